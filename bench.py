@@ -22,6 +22,13 @@ batch of one C2 matrix per rank.  The time is the max over ranks.
 --workload c1 | c3 | c4 | c4o | c5 measures the other BASELINE.json configs; c5h the
 north_star headline (one OPT-30B layer at 70%, with rocSPARSE per shape).
 
+A plain run does what the headline figure needs: set-up, the plan search, the warm-up and
+timed steps, the result line.  `--full` adds everything measured beside it: the rocSPARSE
+comparison (with our fp32 plan search), the CPU baseline, the north_star layer object of the
+C2 line, the hot-cache kernel time and the STREAM-copy rate.  `--dump-outputs DIR` writes the
+C arrays of the last timed step as DIR/<name>.npy; B is seeded, so two runs with the same
+arguments compute the same arrays.
+
 Prints one JSON line on rank 0."""
 import argparse
 import ctypes
@@ -77,7 +84,17 @@ def parse():
     ap.add_argument("--sparsity", type=float, default=0.7)
     ap.add_argument("--config", action="append", default=[], metavar="KEY=INT",
                     help="engine switch (gs_set_config_int), e.g. BM_VARIANT=1; repeatable")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the rocSPARSE comparison (fp16 and the fp32 "
+                         "plan search), the CPU baseline, the north_star layer object, the hot-cache kernel time and "
+                         "the STREAM-copy rate (each still has its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its C arrays) to "
+                         "DIR/<name>.npy as float32 (at most 64 MB: a seeded row sample of larger outputs)")
+    a = ap.parse_args()
+    if not a.full:  # a plain run measures the headline figure only
+        a.no_rocsparse = a.no_cpu = a.no_north_star = True
+    return a
 
 
 def resolve_workload(a, world):
@@ -334,6 +351,8 @@ def run_c5(args, torch, gsa, ds, rank, world, local, dev, dist):
         dist.barrier()
     torch.cuda.synchronize()
     wall, ev_s = timed_batch(step, streams, args.steps, torch, marked=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch_outputs(step), rank, world)
     wall = max_over_ranks(wall, dist, torch)
     ev_s = max_over_ranks(ev_s, dist, torch)
     if dist is not None:
@@ -436,15 +455,16 @@ def batch_step(launches, N, torch, n_streams, group=False):
         gstep.launches = lambda: [n for bat, _ in bats for n in bat.launches()]  # entries per launch
         return gstep, streams
     raw = []
-    for i, (p, r, b, c, _) in enumerate(launches):
+    for i, (p, r, b, c, k) in enumerate(launches):
         if n_streams > 1:
             c = torch.empty_like(c)
-        raw.append((p, r, b.data_ptr(), c.data_ptr(), streams[i % len(streams)].cuda_stream, c))
+        raw.append((p, r, b.data_ptr(), c.data_ptr(), streams[i % len(streams)].cuda_stream, c, k))
 
     def step():
-        for plan, r, b, c, s, _ in raw:
+        for plan, r, b, c, s, _, _ in raw:
             plan.spmm_raw(b, c, N, r, s)
 
+    step.keep = raw  # the C buffers live as long as the step
     return step, streams
 
 
@@ -611,6 +631,8 @@ def headline_layer(args, torch, gsa, ds, rank, local, dev, choice, steps, warmup
         step()
     torch.cuda.synchronize()
     wall, ev_s = timed_batch(step, streams, steps, torch, marked=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch_outputs(step))
     ms_step = ev_s / steps * 1e3
     nnz_l, flops_l, alg_l = layer_consts(N, sp)
     plan_of = {k: (per_shape[k]["plan"] if per_shape else cand_key(choice[k])) for k in bt.C5_SHAPES}
@@ -769,9 +791,49 @@ def build_plan(gsa, M, K, row, col, val, cand, N, dt, local, rotation_mb, e, tdt
     reps = replicas_for(info, K, N, e, rotation_mb)
     for _ in range(reps - 1):
         plan.add_replica()
-    Bs = [torch.randn((K, N), device=dev, dtype=tdt) for _ in range(reps)]
+    # one seeded B, the replicas its copies at their own addresses (the rotation still streams a
+    # different copy every step): whichever plan wins the search and however many replicas it
+    # rotates, every step computes the same A x B, so --dump-outputs compares from run to run
+    g = torch.Generator(device=dev)
+    g.manual_seed(B_SEED)
+    B0 = torch.randn((K, N), device=dev, dtype=tdt, generator=g)
+    Bs = [B0] + [B0.clone() for _ in range(reps - 1)]
     Cs = [torch.empty((M, N), device=dev, dtype=tdt) for _ in range(reps)]
     return plan, Bs, Cs, reps, t_plan
+
+
+B_SEED = 20
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` (name -> 2-D device tensor, the C of a timed SpMM) as float32
+    DIR/<name>.npy (rank<r>_<name>.npy with several ranks).  Past 64 MB in all (an equal part of
+    it per rank), every array keeps the same share of its rows, drawn once from a fixed seed and
+    sorted: the same rows in every run of the same arguments."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    share = min(1.0, DUMP_LIMIT_BYTES / world / max(1, total))
+    rng = np.random.default_rng(0)
+    for name, t in arrays.items():
+        if share < 1.0:
+            keep = np.sort(rng.choice(t.shape[0], size=max(1, int(t.shape[0] * share)), replace=False))
+            t = t.index_select(0, torch.from_numpy(keep).to(t.device))
+        if world > 1:
+            name = "rank%d_%s" % (rank, name)
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
+
+
+def batch_outputs(step):
+    """the distinct C buffers a batch step writes (batch_step's keep list), in launch order, by name"""
+    out, seen = {}, set()
+    for ent in step.keep:
+        c, k = ent[-2], ent[-1]
+        if c.data_ptr() not in seen:
+            seen.add(c.data_ptr())
+            out["C_%03d_%s" % (len(out), k)] = c
+    return out
 
 
 def main():
@@ -930,14 +992,18 @@ def main():
     # the measurement: W untimed warm-up steps, exactly K timed steps
     if shards is not None and args.shard == "nnz" and dist is not None:
         wall, ev_s = time_plan_combined(plan, Bs, Cs, N, args.steps, args.warmup, torch, dist, shards, rank)
+        last = (args.steps - 1) % reps
     else:
         wall, ev_s = time_plan(plan, Bs, Cs, N, args.steps, args.warmup, torch, dist)
-    hot_ms = event_ms(plan, Bs, Cs, 100, torch, rotate=False)
+        last = (args.warmup + args.steps - 1) % reps  # the (B, C) pair of the last timed step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"C": Cs[last]}, rank, world)
+    hot_ms = event_ms(plan, Bs, Cs, 100, torch, rotate=False) if args.full else None
     for p_ in losers:
         p_.free()
     losers.clear()
     torch.cuda.empty_cache()
-    copy_gbs = stream_copy_gbs(torch, dev)
+    copy_gbs = stream_copy_gbs(torch, dev) if args.full else None
     # value and ms_per_step from the HIP events around the K timed steps (max over ranks);
     # the host wall time of the same region is reported beside them
     ev_ms = ev_s / args.steps * 1e3
@@ -985,16 +1051,18 @@ def main():
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(ev_ms, 5),
-                     "hot_cache_kernel_ms": round(hot_ms, 5),
-                     "measured_copy_gbs": copy_gbs, "frac_of_measured_copy": round(achieved / copy_gbs, 4),
                      "guide_copy_gbs": GUIDE_COPY_GBS, "frac_of_guide_copy": round(achieved / GUIDE_COPY_GBS, 4),
-                     "measured_copy_note": "STREAM copy measured on this GPU after the timed region (SURVEY 8d): "
-                                           "torch's copy of 2 GiB fp32, bytes read + written -- not a tuned copy "
-                                           "kernel, so it reads below the 6.29 TB/s MI355X_MICROARCH.md measures "
-                                           "(guide_copy_gbs); `peak` stays the 8 TB/s datasheet figure",
                      "mfma_util": mfma["mfma_util"] if mfma else None, "mfma": mfma},
         "variants": variants,
     }
+    if args.full:  # the two figures that take GPU runs of their own
+        out["roofline"].update({
+            "hot_cache_kernel_ms": round(hot_ms, 5),
+            "measured_copy_gbs": copy_gbs, "frac_of_measured_copy": round(achieved / copy_gbs, 4),
+            "measured_copy_note": "STREAM copy measured on this GPU after the timed region (SURVEY 8d): "
+                                  "torch's copy of 2 GiB fp32, bytes read + written -- not a tuned copy "
+                                  "kernel, so it reads below the 6.29 TB/s a tuned copy kernel reaches on an "
+                                  "MI355X (guide_copy_gbs); `peak` stays the 8 TB/s datasheet figure"})
     if args.n_sweep and rank == 0:
         out["n_sweep"] = n_sweep(gsa, M, K, row, col, val, cands, args, dt, local, e, tdt, dev, torch, nnz)
     if rank == 0 and not args.no_rocsparse:
@@ -1014,7 +1082,7 @@ def main():
         # of HBM) timed in the same run: one layer, the headline plans, no search
         from generalsparse_amd import batch as bt
         a2 = argparse.Namespace(**vars(args))
-        a2.group, a2.streams = 1, 1
+        a2.group, a2.streams, a2.dump_outputs = 1, 1, None
         try:
             # the reference's protocol (100 timed launches after 10 warm-ups, baseline/base_cusparse/
             # spmm.cu:136-158) after 200 ms of untimed layer steps (the plans are built while the GPU idles)

@@ -37,7 +37,7 @@ print('$2', d['config'].get('plan'), d['config'].get('kernel'), 'us', round(d['m
 }
 bench() {  # <label> <bench args...>
   local tag=$1; shift
-  timeout -k 10 900 python3 -u bench.py "$@" > $OUT/b_$tag.log 2>&1
+  timeout -k 10 900 python3 -u bench.py --full "$@" > $OUT/b_$tag.log 2>&1
   line b_$tag.log "$tag"
 }
 for ex in "$@"; do

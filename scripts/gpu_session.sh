@@ -27,13 +27,13 @@ fi
 for wl in $WLS; do
   steps=$(bench_steps $wl); psteps=$(prof_steps $wl)
   if has bench; then
-    timeout -k 10 900 python3 -u bench.py --workload $wl --steps $steps --warmup 20 ${BENCH_ARGS:-} > $OUT/bench_$wl.log 2>&1
+    timeout -k 10 900 python3 -u bench.py --workload $wl --steps $steps --warmup 20 --full ${BENCH_ARGS:-} > $OUT/bench_$wl.log 2>&1
     tail -1 $OUT/bench_$wl.log | cut -c1-300
   fi
   if has prof; then
     # GS_BENCH_MARK=1: spin-kernel markers around the timed region, so timed_stats.py keeps only its dispatches
     GS_BENCH_MARK=1 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$wl -o p -- \
-      python3 bench.py --workload $wl --steps $psteps --warmup 10 --no-cpu --no-rocsparse ${BENCH_ARGS:-} > $OUT/prof_$wl.log 2>&1
+      python3 bench.py --workload $wl --steps $psteps --warmup 10 --full --no-cpu --no-rocsparse ${BENCH_ARGS:-} > $OUT/prof_$wl.log 2>&1
     python3 scripts/timed_stats.py $OUT/prof_$wl $OUT/prof_${wl}_timed_stats.csv > /dev/null || echo "timed_stats $wl: no marked region"
     echo "prof $wl done"
   fi
