@@ -1,0 +1,225 @@
+// hip_code/kernel_common.hpp -- what the kernel family headers share: the raw vector types,
+// the fp32 load / store / atomic helpers, the read-once loads, xcd_block, fma_row, and the
+// helpers of more than one matrix-core family (fragment types, b_piece, ks_slab_wait).
+// A family header includes this one and nothing else of hip_code/.
+#pragma once
+
+#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "idx_formula.hpp"
+#include "kernel_consts.hpp"
+
+namespace gsk {
+
+typedef _Float16 f16;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+template <int BYTES> struct raw_vec;
+template <> struct raw_vec<2> { typedef uint16_t t; };
+template <> struct raw_vec<4> { typedef uint32_t t; };
+template <> struct raw_vec<8> { typedef uint2 t; };
+template <> struct raw_vec<16> { typedef uint4 t; };
+struct alignas(16) u32x8 { uint4 lo, hi; };
+template <> struct raw_vec<32> { typedef u32x8 t; };
+
+// CF contiguous values -> fp32 (one vector load)
+template <class VT, int CF>
+__device__ __forceinline__ void load_f32(const VT *__restrict__ p, float (&out)[CF]) {
+    typedef typename raw_vec<CF * sizeof(VT)>::t R;
+    R r = *reinterpret_cast<const R *>(p);
+    VT tmp[CF];
+    __builtin_memcpy(tmp, &r, sizeof(R));
+#pragma unroll
+    for (int k = 0; k < CF; k++) out[k] = (float)tmp[k];
+}
+
+template <class VT, int CF>
+__device__ __forceinline__ void store_f32(VT *__restrict__ p, const float (&in)[CF]) {
+    typedef typename raw_vec<CF * sizeof(VT)>::t R;
+    VT tmp[CF];
+#pragma unroll
+    for (int k = 0; k < CF; k++) tmp[k] = (VT)in[k];
+    R r;
+    __builtin_memcpy(&r, tmp, sizeof(R));
+    *reinterpret_cast<R *>(p) = r;
+}
+
+// Loads of the operand a launch reads exactly once (A's entries, groups, panels).  GS_A_NT=1
+// (make A_NT=1): the non-temporal form (global_load ... nt), which the XCD's L2 holds at low
+// retention, so the stream does not push out the rows of B that other workgroups re-read.
+template <class T>
+__device__ __forceinline__ T ld_once(const T *p) {
+#if defined(GS_A_NT) && GS_A_NT
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+// the same, chosen per instantiation (k_mfma_ks KS_NT, k_nm_mfma NM_NT): NT loads bypass the CU's
+// L1 and stream through L2 (MI355X_MICROARCH.md: nt loads are L2-served)
+template <bool NT, class T>
+__device__ __forceinline__ T ld_once_if(const T *p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return ld_once(p);
+}
+template <int BYTES> struct raw_ext;
+template <> struct raw_ext<1> { typedef uint8_t t; };
+template <> struct raw_ext<2> { typedef uint16_t t; };
+template <> struct raw_ext<4> { typedef uint32_t t; };
+template <> struct raw_ext<8> { typedef u32x2 t; };
+template <> struct raw_ext<16> { typedef u32x4 t; };
+
+// SCF contiguous sparse entries (cols or vals) in one load (read once: ld_once)
+template <class T, int SCF>
+__device__ __forceinline__ void load_raw(const T *__restrict__ p, T (&out)[SCF]) {
+    if constexpr (SCF * sizeof(T) <= 16) {
+        typedef typename raw_ext<SCF * sizeof(T)>::t R;
+        R r = ld_once(reinterpret_cast<const R *>(p));
+        __builtin_memcpy(out, &r, sizeof(R));
+    } else {
+        static_assert(SCF * sizeof(T) == 32, "8 to 32 bytes");
+        u32x4 r[2] = {ld_once(reinterpret_cast<const u32x4 *>(p)), ld_once(reinterpret_cast<const u32x4 *>(p) + 1)};
+        __builtin_memcpy(out, r, 32);
+    }
+}
+
+template <int CF>
+__device__ __forceinline__ void wave_reduce_slots(float (&acc)[CF], int X) {
+    for (int off = X; off < 64; off <<= 1) {
+#pragma unroll
+        for (int k = 0; k < CF; k++) acc[k] += __shfl_xor(acc[k], off, 64);
+    }
+}
+
+template <class VT, int CF>
+__device__ __forceinline__ void atomic_add_vals(VT *p, const float (&v)[CF]);
+
+template <>
+__device__ __forceinline__ void atomic_add_vals<float, 1>(float *p, const float (&v)[1]) {
+    unsafeAtomicAdd(p, v[0]);
+}
+template <>
+__device__ __forceinline__ void atomic_add_vals<float, 4>(float *p, const float (&v)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) unsafeAtomicAdd(p + k, v[k]);
+}
+template <>
+__device__ __forceinline__ void atomic_add_vals<float, 8>(float *p, const float (&v)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) unsafeAtomicAdd(p + k, v[k]);
+}
+template <>
+__device__ __forceinline__ void atomic_add_vals<f16, 8>(f16 *p, const float (&v)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {
+        __half2 h = __floats2half2_rn(v[k], v[k + 1]);
+        unsafeAtomicAdd(reinterpret_cast<__half2 *>(p + k), h);
+    }
+}
+template <>
+__device__ __forceinline__ void atomic_add_vals<f16, 1>(f16 *p, const float (&v)[1]) {
+    unsafeAtomicAdd(reinterpret_cast<__half *>(p), __float2half(v[0]));
+}
+
+// XCD-aware block numbering (cdna_hip_programming.md §5.5 T1): blocks b and b + 8 are
+// observed to share an XCD (round-robin dispatch, MI355X_MICROARCH.md §Workgroup dispatch),
+// so consecutive blockIdx read the neighbouring cache lines of A's streams from eight
+// different L2s.  The bijective renumbering gives each XCD one contiguous range of
+// logical block ids instead; a speed choice only, any placement stays correct.
+__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
+#ifdef GS_NO_XCD_SWIZZLE  // A/B diagnostic builds only
+    return b;
+#endif
+    const uint32_t q = n >> 3, r = n & 7u, x = b & 7u;
+    return (x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + (b >> 3);
+}
+
+// one sparse entry times a CF-wide B segment
+template <class VT, int CF>
+__device__ __forceinline__ void fma_row(float (&acc)[CF], float v, const VT *__restrict__ brow) {
+    float b[CF];
+    load_f32<VT, CF>(brow, b);
+#pragma unroll
+    for (int k = 0; k < CF; k++) acc[k] = __builtin_fmaf(v, b[k], acc[k]);
+}
+
+// matrix-core operand and accumulator fragments (k_mfma_*, k_nm_mfma*; f4v also k_lds_rows*)
+typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+typedef short s4v __attribute__((ext_vector_type(4)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s4v lds_s4v;
+typedef _Float16 h16v __attribute__((ext_vector_type(16)));
+// 8 bytes at a 2-byte-aligned address (k_mfma_kb / k_mfma_bm value windows)
+typedef uint32_t u32x2_a2 __attribute__((ext_vector_type(2), aligned(2)));
+
+// the place of 32-byte piece p of LDS B row k (a 16*CT-column tile): XOR-permuted so that the
+// transposed fragment reads (ds_read_b64_tr_b16) are conflict-free
+template <int CT>
+__device__ __forceinline__ uint32_t b_piece(uint32_t k, uint32_t p) {
+    uint32_t sw;
+    if constexpr (CT == 1) sw = 0;
+    else if constexpr (CT == 2) sw = (k >> 3) & 1u;
+    else if constexpr (CT == 4) sw = ((k >> 1) & 1u) | (((k >> 3) & 1u) << 1);
+    else sw = (k & 3u) | (((k >> 3) & 1u) << 2);
+    return p ^ (sw & (uint32_t)(CT - 1));
+}
+
+// K-split combine: the last ticket holder's read of 4 words of another workgroup's slab
+// (each word tagged in its low mantissa bit): agent-scope (sc1) loads until every tag reads
+// `tag`.  The writer holds an earlier ticket, so it is resident and its stores are issued or
+// about to be; the wait is bounded by wall time (s_memrealtime, 100 MHz: 0.2 s) all the same.
+// Past the bound the words read as NaN and bit 0 of the plan replica's device error word
+// (`err`, the word after the arrival counters) is set: gs_plan_device_status reports it as
+// GS_ERR_DEVICE, so a lost slab is an error at the C ABI, not silent NaNs in C.  `force`
+// (experiments build, KS_FORCE_TIMEOUT) takes the timeout path at once (the test of that chain).
+__device__ __forceinline__ u32x4 ks_slab_wait(const uint32_t *src, uint32_t tag, uint32_t *err, bool force) {
+    u32x4 w;
+    auto load4 = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; i++) w[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto stale = [&]() { return (((w[0] ^ tag) | (w[1] ^ tag) | (w[2] ^ tag) | (w[3] ^ tag)) & 1u) != 0u; };
+    bool lost = force;
+    if (!lost) {
+        load4();
+        if (stale()) {
+            // the bound needs 0.2 s of wall time AND 1024 polls since the last gap: a gap of
+            // over 1 ms between two polls means this wave was switched out (CWSR time slicing),
+            // so the bound restarts rather than counting the time the writer could not run
+            uint64_t t0 = __builtin_amdgcn_s_memrealtime(), prev = t0;
+            uint32_t polls = 0;
+            do {
+                const uint64_t t = __builtin_amdgcn_s_memrealtime();
+                if (t - prev > 100000ull) {
+                    t0 = t;
+                    polls = 0;
+                }
+                prev = t;
+                if (t - t0 > 20000000ull && polls >= 1024u) {
+                    lost = true;
+                    break;
+                }
+                polls++;
+                __builtin_amdgcn_s_sleep(2);
+                load4();
+            } while (stale());
+        }
+    }
+    if (lost) {
+        w = u32x4{0x7fc00000u | tag, 0x7fc00000u | tag, 0x7fc00000u | tag, 0x7fc00000u | tag};
+        __hip_atomic_fetch_or(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return w;
+}
+#ifdef GS_EXPERIMENTS
+#define GS_KS_FORCE(prio) (((prio) & 16u) != 0u)
+#else
+#define GS_KS_FORCE(prio) false
+#endif
+
+}  // namespace gsk

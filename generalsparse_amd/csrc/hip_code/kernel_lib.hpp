@@ -9,6 +9,9 @@
 // vector-loaded; B rows are gathered through L1/L2 (B is small and shared).
 // Accumulation is always fp32 (the reference accumulates fp16 in half).
 //
+// The emitted programs include this file and get every family.  Families with a header of
+// their own are included below; the others are still defined here.
+//
 // Families (selected by code_generator::compile from the reduction tokens):
 //   k_thread_total   K1: X lanes per BMT row, rows sorted + col-padded (SCF-aligned)
 //   k_warp_rows      K4: one wave per BMW, nnz split over S slots, xor-shuffle reduce
@@ -18,151 +21,25 @@
 //                       head/tail partials combined per wave, then atomics
 //   k_row_chunks     K5/K7: col-direction BMTs (chunks of one row), segmented
 //                       slot tree + a row carry per wave
+//   k_lds_rows[_dma,_rs] K4 with B chunks staged in LDS, one workgroup per BMTB
+//   k_mfma_rows      BMTB row blocks on the matrix cores, one workgroup per row block
+//   k_mfma_ks[_group] the same with K split over workgroups: mfma_ks.hpp
+//   k_nm_mfma        2:4 panels on the sparse matrix cores
+//   k_merge_path     merge-path levels (+ k_permute_rows, k_merge_fixup)
+//   experiments build only: k_mfma_kb, k_mfma_bm, k_mfma_bm2: mfma_bm_exp.hpp;
+//                       k_nm_mfma_ks, k_nm_mfma4: nm_mfma_exp.hpp
+// kernel_common.hpp: what the families share; host_layouts.hpp: the host-only gsk_host helpers
 #pragma once
 
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "kernel_common.hpp"
 
-#include <type_traits>
-
-#include "idx_formula.hpp"
-#include "kernel_consts.hpp"
+#include "mfma_ks.hpp"
+#ifdef GS_EXPERIMENTS  // opt-in kernels measured slower than the default ones
+#include "mfma_bm_exp.hpp"
+#include "nm_mfma_exp.hpp"
+#endif
 
 namespace gsk {
-
-typedef _Float16 f16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-template <int BYTES> struct raw_vec;
-template <> struct raw_vec<2> { typedef uint16_t t; };
-template <> struct raw_vec<4> { typedef uint32_t t; };
-template <> struct raw_vec<8> { typedef uint2 t; };
-template <> struct raw_vec<16> { typedef uint4 t; };
-struct alignas(16) u32x8 { uint4 lo, hi; };
-template <> struct raw_vec<32> { typedef u32x8 t; };
-
-// CF contiguous values -> fp32 (one vector load)
-template <class VT, int CF>
-__device__ __forceinline__ void load_f32(const VT *__restrict__ p, float (&out)[CF]) {
-    typedef typename raw_vec<CF * sizeof(VT)>::t R;
-    R r = *reinterpret_cast<const R *>(p);
-    VT tmp[CF];
-    __builtin_memcpy(tmp, &r, sizeof(R));
-#pragma unroll
-    for (int k = 0; k < CF; k++) out[k] = (float)tmp[k];
-}
-
-template <class VT, int CF>
-__device__ __forceinline__ void store_f32(VT *__restrict__ p, const float (&in)[CF]) {
-    typedef typename raw_vec<CF * sizeof(VT)>::t R;
-    VT tmp[CF];
-#pragma unroll
-    for (int k = 0; k < CF; k++) tmp[k] = (VT)in[k];
-    R r;
-    __builtin_memcpy(&r, tmp, sizeof(R));
-    *reinterpret_cast<R *>(p) = r;
-}
-
-// Loads of the operand a launch reads exactly once (A's entries, groups, panels).  GS_A_NT=1
-// (make A_NT=1): the non-temporal form (global_load ... nt), which the XCD's L2 holds at low
-// retention, so the stream does not push out the rows of B that other workgroups re-read.
-template <class T>
-__device__ __forceinline__ T ld_once(const T *p) {
-#if defined(GS_A_NT) && GS_A_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-// the same, chosen per instantiation (k_mfma_ks KS_NT, k_nm_mfma NM_NT): NT loads bypass the CU's
-// L1 and stream through L2 (MI355X_MICROARCH.md: nt loads are L2-served)
-template <bool NT, class T>
-__device__ __forceinline__ T ld_once_if(const T *p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return ld_once(p);
-}
-template <int BYTES> struct raw_ext;
-template <> struct raw_ext<1> { typedef uint8_t t; };
-template <> struct raw_ext<2> { typedef uint16_t t; };
-template <> struct raw_ext<4> { typedef uint32_t t; };
-template <> struct raw_ext<8> { typedef u32x2 t; };
-template <> struct raw_ext<16> { typedef u32x4 t; };
-
-// SCF contiguous sparse entries (cols or vals) in one load (read once: ld_once)
-template <class T, int SCF>
-__device__ __forceinline__ void load_raw(const T *__restrict__ p, T (&out)[SCF]) {
-    if constexpr (SCF * sizeof(T) <= 16) {
-        typedef typename raw_ext<SCF * sizeof(T)>::t R;
-        R r = ld_once(reinterpret_cast<const R *>(p));
-        __builtin_memcpy(out, &r, sizeof(R));
-    } else {
-        static_assert(SCF * sizeof(T) == 32, "8 to 32 bytes");
-        u32x4 r[2] = {ld_once(reinterpret_cast<const u32x4 *>(p)), ld_once(reinterpret_cast<const u32x4 *>(p) + 1)};
-        __builtin_memcpy(out, r, 32);
-    }
-}
-
-template <int CF>
-__device__ __forceinline__ void wave_reduce_slots(float (&acc)[CF], int X) {
-    for (int off = X; off < 64; off <<= 1) {
-#pragma unroll
-        for (int k = 0; k < CF; k++) acc[k] += __shfl_xor(acc[k], off, 64);
-    }
-}
-
-template <class VT, int CF>
-__device__ __forceinline__ void atomic_add_vals(VT *p, const float (&v)[CF]);
-
-template <>
-__device__ __forceinline__ void atomic_add_vals<float, 1>(float *p, const float (&v)[1]) {
-    unsafeAtomicAdd(p, v[0]);
-}
-template <>
-__device__ __forceinline__ void atomic_add_vals<float, 4>(float *p, const float (&v)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) unsafeAtomicAdd(p + k, v[k]);
-}
-template <>
-__device__ __forceinline__ void atomic_add_vals<float, 8>(float *p, const float (&v)[8]) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) unsafeAtomicAdd(p + k, v[k]);
-}
-template <>
-__device__ __forceinline__ void atomic_add_vals<f16, 8>(f16 *p, const float (&v)[8]) {
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        __half2 h = __floats2half2_rn(v[k], v[k + 1]);
-        unsafeAtomicAdd(reinterpret_cast<__half2 *>(p + k), h);
-    }
-}
-template <>
-__device__ __forceinline__ void atomic_add_vals<f16, 1>(f16 *p, const float (&v)[1]) {
-    unsafeAtomicAdd(reinterpret_cast<__half *>(p), __float2half(v[0]));
-}
-
-// XCD-aware block numbering (cdna_hip_programming.md §5.5 T1): blocks b and b + 8 are
-// observed to share an XCD (round-robin dispatch, MI355X_MICROARCH.md §Workgroup dispatch),
-// so consecutive blockIdx read the neighbouring cache lines of A's streams from eight
-// different L2s.  The bijective renumbering gives each XCD one contiguous range of
-// logical block ids instead; a speed choice only, any placement stays correct.
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
-#ifdef GS_NO_XCD_SWIZZLE  // A/B diagnostic builds only
-    return b;
-#endif
-    const uint32_t q = n >> 3, r = n & 7u, x = b & 7u;
-    return (x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + (b >> 3);
-}
-
-// one sparse entry times a CF-wide B segment
-template <class VT, int CF>
-__device__ __forceinline__ void fma_row(float (&acc)[CF], float v, const VT *__restrict__ brow) {
-    float b[CF];
-    load_f32<VT, CF>(brow, b);
-#pragma unroll
-    for (int k = 0; k < CF; k++) acc[k] = __builtin_fmaf(v, b[k], acc[k]);
-}
 
 // ---------------------------------------------------------------------------
 // K1 thread_total: the row-sorted, col-padded plan (sort_operator +
@@ -1024,7 +901,6 @@ __device__ __forceinline__ void static_for(F &&f) {
     }
 }
 
-typedef float f4v __attribute__((ext_vector_type(4)));
 // K split (ksp > 1, LDS_KSPLIT): workgroup u = g * ksp + q walks the chunks [q * ncs, +ncs) of
 // BMTB g only, publishes its rows' fp32 partials and the last of the ksp workgroups sums them in q
 // order (deterministic) -- for plans with too few BMTBs to fill the CUs (upload rule).
@@ -1534,21 +1410,6 @@ __global__ __launch_bounds__(1024) void k_lds_rows_rs(
 // times a non-finite B value gives NaN: the kernel multiplies the row block's
 // whole tile.
 // ---------------------------------------------------------------------------
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s4v lds_s4v;
-
-template <int CT>
-__device__ __forceinline__ uint32_t b_piece(uint32_t k, uint32_t p) {
-    uint32_t sw;
-    if constexpr (CT == 1) sw = 0;
-    else if constexpr (CT == 2) sw = (k >> 3) & 1u;
-    else if constexpr (CT == 4) sw = ((k >> 1) & 1u) | (((k >> 3) & 1u) << 1);
-    else sw = (k & 3u) | (((k >> 3) & 1u) << 2);
-    return p ^ (sw & (uint32_t)(CT - 1));
-}
-
 
 // STAMPS (diagnostic build only, gs_debug_mfma_timeline): lane 0 of the first
 // compute / B / entry wave records s_memtime at phase boundaries
@@ -1973,1319 +1834,6 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void k_mfma_rows(
 }
 
 // ---------------------------------------------------------------------------
-// k_mfma_ks -- BMTB row blocks on the matrix cores with K split over S workgroups
-// and every wave running on its own (the default matrix-core kernel for row blocks of
-// >= 40 rows).
-// Why: a workgroup that owns a row block over all of K streams all of B (327 KB on C2)
-// for its ~120 KB of A; one CU takes in ~50-70 GB/s, so B, not A, set the time
-// (scripts/probes/probe_floor.hip: loading A + B alone takes 10.9 us at S = 1, 7.2 us at
-// S = 4).  Here workgroup (g, q) owns row block g over the K range [q*KR, q*KR + KR) and
-// reads only that slice of B (KR rows).
-// Wave w owns the range's 32-column k-steps w, w+W, ... and runs them with no
-// workgroup barrier until the end: per k-step it loads (D steps ahead, into registers)
-// the step's 32 B rows and its entries (upload layout: the step's groups back to back,
-// each 8 x [u16 halfword position in the wave's dense image] + 8 x [f16 value], found by
-// the step's {first group, group count} record, loaded D steps ahead of the groups;
-// padding inside a group writes 0 into the image's zero row; NT: the groups by non-temporal
-// loads when NTL & 1 (KS_NT; B's rows when NTL & 2, not instantiated: slower), stores the B rows into its private stage (32-B pieces
-// permuted by b_piece so the ds_read_b64_tr_b16 fragment reads are conflict-free),
-// scatters the entries into its private image of 16*RT+1 rows x 96 B (conflict-free
-// ds_read_b128), reads the RT A fragments and the CT B fragments, writes zeros back at
-// the entries' positions, and runs RT x CT v_mfma_f32_16x16x32_f16 into fp32
-// accumulators.  Every step issues the same loads (steps past the wave's last read the
-// first B rows and the spare group: one cached line each), so the compiler's waits
-// stay counted ones.  At the end the W partial tiles are summed through LDS in wave
-// order; with S > 1 each workgroup publishes its fp32 slab (16-B sc1 write-through
-// stores, drained by every storing wave, then one arrival add), and the last of the row
-// block's S workgroups sums the S slabs in q order (deterministic, whichever arrives
-// last) and writes C: the hand-off form of MI355X_MICROARCH.md §Workgroup dispatch,
-// table row 1 (sc1 stores + vmcnt(0) + barrier + one agent add; the last adder, told by
-// the returned value, loads with sc1 loads after a barrier).  Workgroup order: unit
-// u = g*S + q, XCD-contiguous (xcd_block), so a row block's S workgroups are normally on
-// one XCD (speed only).  Rows of B past K are stored as zeros; a zero of the dense tile
-// times a non-finite in-range B value gives NaN for the row block (DESIGN.md deviation,
-// as for k_mfma_rows).
-// ---------------------------------------------------------------------------
-// s_waitcnt immediate (gfx9 encoding) waiting for vmcnt <= N only (expcnt / lgkmcnt at their maxima)
-template <int N>
-__device__ constexpr int vmcnt_imm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is six bits");
-    return (N & 0xF) | ((N >> 4) << 14) | 0x70 | 0xF00;
-}
-
-// kKsStride, ks_image_bytes, ks_lds_bytes: kernel_consts.hpp
-// 8 bytes at a 2-byte-aligned address (k_mfma_kb / k_mfma_bm value windows)
-typedef uint32_t u32x2_a2 __attribute__((ext_vector_type(2), aligned(2)));
-
-// K-split combine: the last ticket holder's read of 4 words of another workgroup's slab
-// (each word tagged in its low mantissa bit): agent-scope (sc1) loads until every tag reads
-// `tag`.  The writer holds an earlier ticket, so it is resident and its stores are issued or
-// about to be; the wait is bounded by wall time (s_memrealtime, 100 MHz: 0.2 s) all the same.
-// Past the bound the words read as NaN and bit 0 of the plan replica's device error word
-// (`err`, the word after the arrival counters) is set: gs_plan_device_status reports it as
-// GS_ERR_DEVICE, so a lost slab is an error at the C ABI, not silent NaNs in C.  `force`
-// (experiments build, KS_FORCE_TIMEOUT) takes the timeout path at once (the test of that chain).
-__device__ __forceinline__ u32x4 ks_slab_wait(const uint32_t *src, uint32_t tag, uint32_t *err, bool force) {
-    u32x4 w;
-    auto load4 = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; i++) w[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    auto stale = [&]() { return (((w[0] ^ tag) | (w[1] ^ tag) | (w[2] ^ tag) | (w[3] ^ tag)) & 1u) != 0u; };
-    bool lost = force;
-    if (!lost) {
-        load4();
-        if (stale()) {
-            // the bound needs 0.2 s of wall time AND 1024 polls since the last gap: a gap of
-            // over 1 ms between two polls means this wave was switched out (CWSR time slicing),
-            // so the bound restarts rather than counting the time the writer could not run
-            uint64_t t0 = __builtin_amdgcn_s_memrealtime(), prev = t0;
-            uint32_t polls = 0;
-            do {
-                const uint64_t t = __builtin_amdgcn_s_memrealtime();
-                if (t - prev > 100000ull) {
-                    t0 = t;
-                    polls = 0;
-                }
-                prev = t;
-                if (t - t0 > 20000000ull && polls >= 1024u) {
-                    lost = true;
-                    break;
-                }
-                polls++;
-                __builtin_amdgcn_s_sleep(2);
-                load4();
-            } while (stale());
-        }
-    }
-    if (lost) {
-        w = u32x4{0x7fc00000u | tag, 0x7fc00000u | tag, 0x7fc00000u | tag, 0x7fc00000u | tag};
-        __hip_atomic_fetch_or(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return w;
-}
-#ifdef GS_EXPERIMENTS
-#define GS_KS_FORCE(prio) (((prio) & 16u) != 0u)
-#else
-#define GS_KS_FORCE(prio) false
-#endif
-
-// STAMPS (diagnostic build only, gs_debug_mfma_timeline): lane 0 of every wave records
-// s_memtime into stamps[(workgroup * W + wave) * 32 + slot]: 0 start, 1 loads issued,
-// 3 + i after step i (i < 16), 20 loop done, 21 reduced, 22 end
-// the body of k_mfma_ks for workgroup bx of a launch of nwg workgroups (k_mfma_ks: the
-// whole grid; k_mfma_ks_group: one entry's share of it)
-// P8 (KS_POS8, device_layout.cc pos8_step): tP holds 8 bytes per group -- byte e = bit e of the
-// group's 8 x 16 segment id in bit 7, the entry's (row % 8) << 4 | column % 16 below; the image
-// halfword of a segment sg's entry is 384 * (sg >> 1) + 16 * (sg & 1) + 48 * (b >> 4) + (b & 15)
-template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, bool P8 = false, int NTL = 0>
-__device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_row, const u32x4 *__restrict__ tP,
-                                        const u32x4 *__restrict__ tV, const u32x2 *__restrict__ steps,
-                                        const f16 *__restrict__ B, f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
-                                        uint32_t NS, uint32_t nwg, uint32_t row_base, float *__restrict__ slabs,
-                                        uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps, uint32_t bx,
-                                        uint32_t prio) {
-    constexpr uint32_t RB = 32 * CT;  // bytes per LDS B row (a 16*CT-column tile)
-    constexpr uint32_t UB = 2 * CT;   // 16-B units per B row
-    constexpr uint32_t IMG = ks_image_bytes<RT>();
-    constexpr uint32_t STG = 32u * RB;  // one k-step of B rows
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t u = xcd_block(bx, nwg);
-    const uint32_t g = u / S, q = u - g * S;
-#define GS_KS_STAMP(slot)                                                                          \
-    if constexpr (STAMPS) {                                                                        \
-        if (lane == 0) stamps[((size_t)blockIdx.x * W + wv) * 32u + (slot)] = __builtin_amdgcn_s_memtime(); \
-    }
-    GS_KS_STAMP(0u);
-    const uint32_t k0 = q * NS * 32u;
-    // column tile blockIdx.y: columns [col0, col0 + nv) of B and C (N > 16*CT: several
-    // tiles; N = 8: one partial tile)
-    const uint32_t col0 = blockIdx.y * 16u * CT, nv = min(16u * CT, N - col0);
-    unsigned char *img = lds + wv * (IMG + STG);
-    unsigned char *bst = img + IMG;
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-
-    // ---- this wave's k-steps w, w+W, ...: step s of unit u is record steps[u*NS + s] =
-    // {first group, group count}; a slot's next record is loaded one round (D steps) before
-    // its groups, so the groups' addresses wait on a load issued a round earlier
-    const uint32_t nsw = NS > wv ? (NS - wv + W - 1u) / W : 0u;
-    const size_t ubase = (size_t)u * NS;
-    using PV = typename std::conditional<P8, u32x2, u32x4>::type;
-    const PV *tPp = reinterpret_cast<const PV *>(tP);
-    PV P[D][MAXG];
-    u32x4 V[D][MAXG], BR[D][CT];
-    u32x2 NX[D];      // per slot: record of the step the slot loads next
-    uint32_t CN[D];   // per slot: group count of the step whose groups it holds
-    // the record is read by a vector load (vmcnt, in order with the groups): a scalar load
-    // would share lgkmcnt with the LDS traffic, and every step's lgkmcnt(0) before its
-    // fragments would then wait for the newest record as well (80% sparsity: +3-9%)
-    uint32_t vz;
-    __asm__ volatile("v_mov_b32 %0, 0" : "=v"(vz));
-    auto rec_of = [&](uint32_t i) -> u32x2 {
-        const uint32_t st = __builtin_amdgcn_readfirstlane(i < nsw ? wv + i * W : 0u);
-        return steps[ubase + st + vz];
-    };
-    // steps past the wave's last re-read the unit's first step (cached; the same lane-varying
-    // load form as a live step, so no path of the loop issues a different count).  The B rows
-    // of a step need no record: they are issued apart from (and, in the prologue, before) the
-    // groups, whose addresses wait for the step's record
-    auto load_b = [&](uint32_t i, u32x4 (&B_)[CT]) {
-        const uint32_t st = __builtin_amdgcn_readfirstlane(i < nsw ? wv + i * W : 0u);
-        const uint32_t kr = k0 + st * 32u;  // first B row of the step
-#pragma unroll
-        for (int c = 0; c < CT; c++) {
-            const uint32_t un = lane + 64u * c;  // 16-B unit of the step's 32 rows
-            const uint32_t k = kr + un / UB, cu = (un % UB) * 8u;
-            // columns past N (a partial column tile: N = 8, 24, ...) read column 0 and are
-            // stored as zeros below
-            B_[c] = ld_once_if<(NTL & 2) != 0>(
-                reinterpret_cast<const u32x4 *>(B + (size_t)(k < K ? k : K - 1u) * N + col0 + (cu < nv ? cu : 0u)));
-        }
-    };
-    // the groups of step i (b0: first group, gc: count), then the record of step i + D
-    auto load_g_at = [&](uint32_t i, uint32_t b0, uint32_t gc, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG],
-                         u32x4 (&V_)[MAXG]) {
-        CN_ = gc;
-        NX_ = rec_of(i + D);
-#pragma unroll
-        for (int j = 0; j < MAXG; j++) {
-            const uint32_t qg = lane + 64u * j;
-            const size_t at = (size_t)b0 + (qg < gc ? qg : 0u);
-            P_[j] = ld_once_if<(NTL & 1) != 0>(tPp + at);
-            V_[j] = ld_once_if<(NTL & 1) != 0>(tV + at);
-        }
-    };
-    auto load_g = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG]) {
-        load_g_at(i, __builtin_amdgcn_readfirstlane(NX_[0]), __builtin_amdgcn_readfirstlane(NX_[1]), NX_, CN_, P_, V_);
-    };
-    // head steps (device_layout.cc ks_tiles::GH, prio bits 8..17): the first D steps of every wave
-    // sit at (unit * min(W * D, NS) + step) * GH, padded with zero-row groups, so the prologue issues their
-    // groups with the B rows at once instead of a record round trip later
-    const uint32_t GH = (prio >> 8) & 0x3ffu;
-    if (GH) {
-#pragma unroll
-        for (int d = 0; d < D; d++) load_b((uint32_t)d, BR[d]);
-#pragma unroll
-        for (int d = 0; d < D; d++) {
-            const uint32_t st = (uint32_t)d < nsw ? wv + (uint32_t)d * W : 0u;
-            load_g_at((uint32_t)d, (u * min((uint32_t)(W * D), NS) + st) * GH, GH, NX[d], CN[d], P[d], V[d]);
-        }
-        for (uint32_t x = lane; x < IMG / 16u; x += 64u) *reinterpret_cast<u32x4 *>(img + x * 16u) = zero4;
-    } else {
-#pragma unroll
-        for (int d = 0; d < D; d++) NX[d] = rec_of((uint32_t)d);
-#pragma unroll
-        for (int d = 0; d < D; d++) load_b((uint32_t)d, BR[d]);
-        for (uint32_t x = lane; x < IMG / 16u; x += 64u) *reinterpret_cast<u32x4 *>(img + x * 16u) = zero4;
-#pragma unroll
-        for (int d = 0; d < D; d++) load_g((uint32_t)d, NX[d], CN[d], P[d], V[d]);
-    }
-    GS_KS_STAMP(1u);
-
-    f4v acc[RT][CT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[rt][ct] = f4v{0.f, 0.f, 0.f, 0.f};
-    uint32_t arow[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) arow[rt] = (16u * rt + (lane & 15u)) * kKsStride + 16u * (lane >> 4);
-
-    // step i on its set, then the set is reloaded with step i + D (issued whether or not
-    // step i exists: every loop iteration issues the same loads)
-    // image halfword of entry e of a group (u16 position, or P8's segment + 7-bit position)
-    auto ent_h = [&](const PV &p, uint32_t hb, int e) -> uint32_t {
-        if constexpr (P8) {
-            const uint32_t b = (p[e >> 2] >> (8 * (e & 3))) & 0x7fu;
-            return hb + 48u * (b >> 4) + (b & 15u);
-        } else {
-            return (p[e >> 1] >> (16 * (e & 1))) & 0xffffu;
-        }
-    };
-    auto grp_hb = [&](const PV &p) -> uint32_t {
-        if constexpr (P8) {
-            const uint32_t x = p[0], y = p[1];
-            const uint32_t sg = ((x >> 7) & 1u) | ((x >> 14) & 2u) | ((x >> 21) & 4u) | ((x >> 28) & 8u) | ((y >> 3) & 16u);
-            return 384u * (sg >> 1) + 16u * (sg & 1u);
-        } else {
-            return 0u;
-        }
-    };
-    auto step = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG], u32x4 (&B_)[CT]) {
-        const bool live = i < nsw;  // wave-uniform
-        const uint32_t gc = CN_;
-        h8v av[RT], bv[CT];
-        if (live) {
-            const uint32_t kr = k0 + (wv + i * W) * 32u;
-            // the step's B rows into the stage (rows past K as zeros)
-#pragma unroll
-            for (int c = 0; c < CT; c++) {
-                const uint32_t un = lane + 64u * c, k = un / UB, s = un % UB;
-                *reinterpret_cast<u32x4 *>(bst + k * RB + b_piece<CT>(k, s >> 1) * 32u + (s & 1u) * 16u) =
-                    kr + k < K && s * 8u < nv ? B_[c] : zero4;
-            }
-            // scatter the step's entries into the image
-#pragma unroll
-            for (int j = 0; j < MAXG; j++) {
-                if (lane + 64u * j < gc) {
-                    const uint32_t hb = grp_hb(P_[j]);
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        const uint32_t h = ent_h(P_[j], hb, e);
-                        const uint16_t v = (uint16_t)((V_[j][e >> 1] >> (16 * (e & 1))) & 0xffffu);
-                        *reinterpret_cast<uint16_t *>(img + h * 2u) = v;
-                    }
-                }
-            }
-            // fragments (LDS runs a wave's operations in order: the reads see the stores)
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++) av[rt] = *reinterpret_cast<const h8v *>(img + arow[rt]);
-            const uint32_t kb = 8u * (lane >> 4);
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                s4v t[2];
-#pragma unroll
-                for (int hh = 0; hh < 2; hh++) {
-                    const uint32_t k = kb + 4u * hh + ((lane & 15u) >> 2);
-                    t[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (lds_s4v *)(bst + k * RB + b_piece<CT>(k, ct) * 32u + (lane & 3u) * 8u));
-                }
-                __builtin_memcpy(&bv[ct], t, 16);
-            }
-            // the image back to zero at the entries' positions
-#pragma unroll
-            for (int j = 0; j < MAXG; j++) {
-                if (lane + 64u * j < gc) {
-                    const uint32_t hb = grp_hb(P_[j]);
-#pragma unroll
-                    for (int e = 0; e < 8; e++) *reinterpret_cast<uint16_t *>(img + ent_h(P_[j], hb, e) * 2u) = (uint16_t)0;
-                }
-            }
-        }
-        load_b(i + D, B_);
-        load_g(i + D, NX_, CN_, P_, V_);
-        if (live) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[rt], bv[ct], acc[rt][ct], 0, 0, 0);
-            if (i < 16u) GS_KS_STAMP(3u + i);
-        }
-    };
-    // prio (KS_PRIO): the younger half of the waves (the second wave of each SIMD, the one
-    // that loses issue arbitration) at s_setprio 1 -- prio & 3 = 1: for its whole loop, 2: for the
-    // first half of its steps
-    const bool young = wv >= W / 2u;
-    if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(1);
-    for (uint32_t i0 = 0; i0 < nsw; i0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; d++) step(i0 + d, NX[d], CN[d], P[d], V[d], BR[d]);
-        if ((prio & 3u) == 2u && young && i0 + D >= nsw / 2u && i0 < nsw / 2u) __builtin_amdgcn_s_setprio(0);
-    }
-    if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(0);
-    GS_KS_STAMP(20u);
-    // ---- K-split ticket: wave 0 takes its row block's arrival ticket as soon as its own
-    // loop ends, so the add's round trip overlaps the partial-tile reduction below
-    uint32_t *arr = arrivals + (size_t)g * gridDim.y + blockIdx.y;
-    uint32_t ticket = 0;
-    if (S > 1 && wv == 0 && lane == 0) ticket = __hip_atomic_fetch_add(arr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // ---- wave partial tiles -> LDS (the trailing loads write registers only), summed in
-    // wave order.  Item t = (tile, lane) of a 16x16 tile: the 4 rows 4*(lane/16)+i of
-    // column lane%16.  When the W partial tiles fit LDS beside the wave images (APART), each
-    // wave stores its tile as soon as its loop ends, without waiting for the others
-    constexpr bool APART = ks_red_apart(CT, RT, W, AP);
-    f4v *red = reinterpret_cast<f4v *>(lds + (APART ? (size_t)W * (IMG + STG) : 0u));
-    constexpr bool HALVES = !APART && ks_red_halves(CT, RT, W);
-    constexpr uint32_t WR = HALVES ? W / 2 : W;  // partial tiles summed from LDS
-    uint32_t *flag = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(red) + (size_t)WR * RT * CT * 1024u);
-    if constexpr (!APART) {
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-    }
-    if constexpr (HALVES) {
-        if (wv >= WR) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) red[(((wv - WR) * RT + rt) * CT + ct) * 64u + lane] = acc[rt][ct];
-        }
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-        if (wv < WR) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) acc[rt][ct] += red[((wv * RT + rt) * CT + ct) * 64u + lane];
-        }
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-    }
-    if (wv < WR) {
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) red[((wv * RT + rt) * CT + ct) * 64u + lane] = acc[rt][ct];
-    }
-    if (S > 1 && wv == 0 && lane == 0) *flag = ticket;  // (waits for the add's return)
-    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __asm__ volatile("" ::: "memory");
-    constexpr uint32_t NI = RT * CT * 64u, NT = 64u * W;
-    const uint32_t r0 = bmtb_first_row[g], R = bmtb_first_row[g + 1] - r0;
-    auto item_sum = [&](uint32_t t) {
-        f4v sum = red[t];
-#pragma unroll
-        for (uint32_t w = 1; w < WR; w++) sum += red[w * NI + t];
-        return sum;
-    };
-    auto store_item = [&](uint32_t t, const f4v &v) {
-        const uint32_t ln = t & 63u, tt = t >> 6, rt = tt / CT, ct = tt % CT;
-        const uint32_t col = 16u * ct + (ln & 15u), rb = 16u * rt + 4u * (ln >> 4);
-        if (col >= nv) return;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; i++)
-            if (rb + i < R) C[(size_t)(row_base + r0 + rb + i) * N + col0 + col] = (f16)v[i];
-    };
-    GS_KS_STAMP(21u);
-    if (S == 1) {
-        for (uint32_t t = tid; t < NI; t += NT) store_item(t, item_sum(t));
-        GS_KS_STAMP(22u);
-        return;
-    }
-    // ---- K-split combine by tagged slabs.  Every fp32 word of a published slab carries
-    // its own validity tag in the low mantissa bit (the reader drops the bit, a 2^-24
-    // relative truncation), so no store needs to be drained before a signal: every workgroup
-    // stores its slab with 16-B write-through (sc1) stores, and the one that drew the last
-    // ticket loads each other slab word with agent-scope (sc1) loads until its tag reads
-    // this launch's value -- its writer holds an earlier ticket, so it is running and its
-    // stores are issued or about to be -- sums the S partials in q order (deterministic) and
-    // writes C.  The tag alternates from launch to launch: the arrival counter holds
-    // (epoch << 16) | arrivals, the tag is epoch ^ 1, and the last workgroup re-arms the
-    // counter with the epoch flipped and no arrivals.  Every slab word then holds the
-    // previous launch's tag when a launch starts (the last workgroup stores its own slab
-    // too), and the zero-filled first state reads as "tag 0, epoch 0" -- so no slab is
-    // cleared after use ((S - 1) fewer slab stores than clearing, the last workgroup's own
-    // store issued before it waits).  Every access to the slabs is sc1 (MI355X_MICROARCH.md
-    // Workgroup dispatch, Valid forms: the R2 granule, here one naturally aligned word).
-    // The next launch on the stream starts after these stores complete.
-    const uint32_t tk = *flag & 0xffffu, tag = ((*flag >> 16) & 1u) ^ 1u;
-    f4v *slab = reinterpret_cast<f4v *>(slabs) + ((size_t)u * gridDim.y + blockIdx.y) * NI;
-    auto tagged = [&](const f4v &v) {
-        u32x4 w;
-        __builtin_memcpy(&w, &v, 16);
-        w[0] = (w[0] & ~1u) | tag; w[1] = (w[1] & ~1u) | tag; w[2] = (w[2] & ~1u) | tag; w[3] = (w[3] & ~1u) | tag;
-        return w;
-    };
-    for (uint32_t t = tid; t < NI; t += NT) {
-        const u32x4 w = tagged(item_sum(t));
-        __asm__ volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(slab + t), "v"(w) : "memory");
-    }
-    if (tk != S - 1u) {
-        GS_KS_STAMP(22u);
-        return;
-    }
-    if (tid == 0) __hip_atomic_store(arr, tag << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const f4v *base = reinterpret_cast<const f4v *>(slabs) + blockIdx.y * NI;
-    const size_t qstride = (size_t)gridDim.y * NI;  // slab of (g, qq) = base + (g*S + qq) * qstride
-    uint32_t *err = arrivals + (size_t)(nwg / S) * gridDim.y;  // the replica's device error word
-    for (uint32_t t = tid; t < NI; t += NT) {
-        f4v sum = {0.f, 0.f, 0.f, 0.f};
-        for (uint32_t qq = 0; qq < S; qq++) {
-            u32x4 w;
-            if (qq == q) {  // truncated as a published word is (whichever workgroup is last: deterministic)
-                w = tagged(item_sum(t));
-            } else {
-                w = ks_slab_wait(reinterpret_cast<const uint32_t *>(base + ((size_t)g * S + qq) * qstride + t), tag, err,
-                                 GS_KS_FORCE(prio));
-            }
-            w[0] &= ~1u; w[1] &= ~1u; w[2] &= ~1u; w[3] &= ~1u;
-            f4v x;
-            __builtin_memcpy(&x, &w, 16);
-            sum += x;
-        }
-        store_item(t, sum);
-    }
-    GS_KS_STAMP(22u);
-#undef GS_KS_STAMP
-}
-
-template <int CT, int RT, int W, int D, int MAXG, bool STAMPS = false, bool AP = true, bool P8 = false, int NTL = 0>
-__global__ __launch_bounds__(64 * W) void k_mfma_ks(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
-                                                    const u32x4 *__restrict__ tP,  // 8 x u16 position per group
-                                                    const u32x4 *__restrict__ tV,  // 8 x f16 value per group
-                                                    const u32x2 *__restrict__ steps,  // per (unit, k-step): first group, count
-                                                    const f16 *__restrict__ B, f16 *__restrict__ C, uint32_t K,
-                                                    uint32_t N, uint32_t S, uint32_t NS, uint32_t nwg,
-                                                    uint32_t row_base, float *__restrict__ slabs,
-                                                    uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps = nullptr,
-                                                    uint32_t prio = 0) {
-    // nwg == gridDim.x (an argument: kernarg preload)
-    ks_body<CT, RT, W, D, MAXG, STAMPS, AP, P8, NTL>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nwg, row_base, slabs,
-                                                arrivals, stamps, blockIdx.x, prio);
-}
-
-#ifdef GS_EXPERIMENTS
-// ---------------------------------------------------------------------------
-// k_mfma_ks_persist (KS_PERSIST = the grid): a persistent grid over
-// the plan's units (row block, K range) -- workgroup b runs unit b, then units pulled from its
-// XCD's head (queue[xcc]: unit grid + xcc + 8 n), until the units run out.  The pull for the next
-// unit is issued as the current one starts (its round trip overlaps the unit's first loads);
-// the units' K-range combine is k_mfma_ks's (tickets + tagged slabs in q order), so C is the
-// same bits as the static launch's whichever workgroup runs a unit.  The last workgroup out
-// re-arms the nine queue words (8 heads + the exit count).
-// ---------------------------------------------------------------------------
-template <int CT, int RT, int W, int D, int MAXG, int NTL = 0>
-__global__ __launch_bounds__(64 * W) void k_mfma_ks_persist(const uint32_t *__restrict__ bmtb_first_row,
-                                                            const u32x4 *__restrict__ tP, const u32x4 *__restrict__ tV,
-                                                            const u32x2 *__restrict__ steps, const f16 *__restrict__ B,
-                                                            f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
-                                                            uint32_t NS, uint32_t nunits, uint32_t row_base,
-                                                            float *__restrict__ slabs, uint32_t *__restrict__ arrivals,
-                                                            uint32_t prio, uint32_t *__restrict__ queue) {
-    __shared__ uint32_t next_sh;
-    uint32_t xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-    xcc &= 7u;
-    const uint32_t grid = gridDim.x;
-    uint32_t u = blockIdx.x, qx = xcc, tried = 0;
-    while (u < nunits) {
-        uint32_t pulled = 0;
-        if (threadIdx.x == 0) pulled = __hip_atomic_fetch_add(queue + qx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ks_body<CT, RT, W, D, MAXG, false, true, false, NTL>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nunits,
-                                                          row_base, slabs, arrivals, nullptr, u, prio);
-        __syncthreads();
-        if (threadIdx.x == 0) next_sh = pulled;
-        __syncthreads();
-        u = grid + qx + 8u * next_sh;
-        __syncthreads();
-        // this XCD's units are done: take the other heads' in turn (correct whatever the placement)
-        while (u >= nunits && ++tried < 8u) {
-            qx = (qx + 1u) & 7u;
-            if (threadIdx.x == 0) next_sh = __hip_atomic_fetch_add(queue + qx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            u = grid + qx + 8u * next_sh;
-            __syncthreads();
-        }
-    }
-    if (threadIdx.x == 0 && __hip_atomic_fetch_add(queue + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == grid - 1u) {
-        for (int i = 0; i < 9; i++) __hip_atomic_store(queue + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-#endif  // GS_EXPERIMENTS (k_mfma_ks_persist)
-
-// ---------------------------------------------------------------------------
-// k_mfma_ks_group -- several k_mfma_ks launches of one instantiation as one grid (a layer's
-// or a batch's SpMMs; gs_spmm_batch): entry i owns workgroups [begin[i], begin[i] + nwg_i) and
-// runs them as its own launch would (begin[i] a multiple of 8: the entry's block numbers keep
-// the XCD residues xcd_block assumes; the blocks up to begin[i+1] exit at once).  One launch instead of one per matrix: no kernel boundary
-// between the matrices, and one matrix's last workgroups overlap the next one's first.  The
-// entries are kernel arguments (ks_group_args, read through the kernarg segment with scalar
-// loads); every entry has its own plan replica (distinct K-range tickets and slabs).
-// ---------------------------------------------------------------------------
-struct ks_entry {  // 96 B
-    const uint32_t *tbr;
-    const u32x4 *tP, *tV;
-    const u32x2 *steps;
-    const f16 *B;
-    f16 *C;
-    float *slabs;
-    uint32_t *arrivals;
-    uint32_t K, S, NS, nwg, row_base, pad0, pad1, pad2;
-};
-// kKsGroupMax: kernel_consts.hpp
-struct ks_group_args {
-    uint32_t begin[kKsGroupMax + 1];  // first workgroup of each entry (+ the total)
-    uint32_t n, N, pad[2];  // pad[0]: k_mfma_ks's prio
-    ks_entry e[kKsGroupMax];
-};
-
-template <int CT, int RT, int W, int D, int MAXG, bool P8 = false, bool AP = true, int NTL = 0>
-__global__ __launch_bounds__(64 * W) void k_mfma_ks_group(ks_group_args args) {
-    const uint32_t bx = blockIdx.x, n = args.n;
-    uint32_t sel = 0;
-#pragma unroll
-    for (int i = 1; i < kKsGroupMax; i++)
-        if ((uint32_t)i < n && args.begin[i] <= bx) sel = (uint32_t)i;
-    sel = __builtin_amdgcn_readfirstlane(sel);
-    const ks_entry &e = args.e[sel];  // kernel arguments: scalar loads at a computed offset
-    if (bx - args.begin[sel] >= e.nwg) return;  // padding up to the next entry's multiple of 8
-    ks_body<CT, RT, W, D, MAXG, false, AP, P8, NTL>(e.tbr, e.tP, e.tV, e.steps, e.B, e.C, e.K, args.N, e.S, e.NS, e.nwg, e.row_base,
-                                       e.slabs, e.arrivals, nullptr, bx - args.begin[sel], args.pad[0] | (e.pad0 << 8));
-}
-
-// ---------------------------------------------------------------------------
-// k_mfma_kb -- k_mfma_ks's K split and per-wave pipeline on k_mfma_bm's bitmap layout: no
-// dense image, no entry scatter.  Per (unit u = row block g x K range q, 32-column k-step s)
-// one 8-byte record per lane l (byte t < RT: the occupancy of row 16t + l%16, columns
-// 32s + 8(l/16) + [0, 8) -- exactly the 8 halves lane l holds of tile t's A operand of
-// v_mfma_f32_16x16x32_f16 -- bytes 6..7: the lane's first value from the step's base
-// sbase[u*NS + s]) and the step's values, lane after lane, tile after tile (host layout:
-// device_layout.cc build_bm_tiles).  A is ~2.4 B per nonzero at 30% density (k_mfma_ks:
-// 4 B).  Wave w runs steps w, w+W, ...: a slot's record and value bounds are loaded one
-// round (D steps) ahead of its values; the values are fetched as whole 16-B units (the
-// step's run from its 16-B-aligned start, NVB KB at most: one full wave load per KB, lanes
-// past the run re-read the first unit) and staged through the wave's LDS slot with B's rows
-// (b_piece-permuted, ds_read_b64_tr_b16 fragments); each lane reads its two 8-byte windows
-// per tile there and expands them into the tile's fragment by four v_perm_b32 with
-// selectors from a 16-entry LDS table.  (The first version loaded the windows straight from
-// HBM: 2 x RT 8-byte loads per lane and step at 2-byte alignment, ~40% of each request
-// used -- C2 21.1 us; the windows alone cost 11.5 us of it.)  Epilogue as k_mfma_ks (wave
-// partial tiles summed in wave order, tagged-slab K-range combine).
-// ---------------------------------------------------------------------------
-// DBG (experiments diagnostics, wrong results): 2 = no value loads, 3 = no B loads
-template <int CT, int RT, int W, int D, int NVB, bool STAMPS, int DBG = 0>
-__device__ __forceinline__ void kb_body(const uint32_t *__restrict__ bmtb_first_row, const uint2 *__restrict__ rec,
-                                        const uint32_t *__restrict__ sbase, const f16 *__restrict__ vals,
-                                        const f16 *__restrict__ B, f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
-                                        uint32_t NS, uint32_t nwg, uint32_t row_base, float *__restrict__ slabs,
-                                        uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps, uint32_t bx,
-                                        uint32_t prio) {
-    static_assert(RT >= 1 && RT <= 6, "six mask bytes per record");
-    static_assert(NVB >= 1 && NVB <= 4, "1..4 KB of values per step");
-    constexpr uint32_t RB = 32 * CT;  // bytes per LDS B row (a 16*CT-column tile)
-    constexpr uint32_t UB = 2 * CT;   // 16-B units per B row
-    constexpr uint32_t STG = 32u * RB;  // one k-step of B rows
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t u = xcd_block(bx, nwg);
-    const uint32_t g = u / S, q = u - g * S;
-#define GS_KB_STAMP(slot)                                                                          \
-    if constexpr (STAMPS) {                                                                        \
-        if (lane == 0) stamps[((size_t)blockIdx.x * W + wv) * 32u + (slot)] = __builtin_amdgcn_s_memtime(); \
-    }
-    GS_KB_STAMP(0u);
-    const uint32_t k0 = q * NS * 32u;
-    const uint32_t col0 = blockIdx.y * 16u * CT, nv = min(16u * CT, N - col0);
-    uint2 *lut = reinterpret_cast<uint2 *>(lds);
-    unsigned char *bst = lds + 128u + wv * (STG + NVB * 1024u);
-    unsigned char *vst = bst + STG;  // the step's values (16-B-aligned run start at byte 0)
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-    if (tid < 16u) lut[tid] = make_uint2(bm_sel(tid, 0), bm_sel(tid, 1));
-
-    const uint32_t nsw = NS > wv ? (NS - wv + W - 1u) / W : 0u;
-    const size_t ubase = (size_t)u * NS;
-    u32x4 BR[D][CT];
-    u32x4 VR[D][NVB];  // per slot: the values of the step it holds (16-B units)
-    uint2 RC[D];       // ... its record
-    uint32_t RL[D];    // ... and its first value's offset (halves) from the run's aligned start
-    uint2 NX[D];       // per slot: record of the step the slot loads next
-    uint32_t NB[D], NE[D];  // ... and its value bounds [sbase[s], sbase[s+1])
-    uint32_t vz;
-    __asm__ volatile("v_mov_b32 %0, 0" : "=v"(vz));
-    auto st_of = [&](uint32_t i) -> uint32_t { return __builtin_amdgcn_readfirstlane(i < nsw ? wv + i * W : 0u); };
-    auto mbyte = [](const uint2 &r, int t) -> uint32_t {
-        return t < 4 ? (r.x >> (8 * t)) & 0xffu : (r.y >> (8 * (t - 4))) & 0xffu;
-    };
-    // record + value bounds of step i (vector loads, in order with the values: see k_mfma_ks)
-    auto load_rec = [&](uint32_t i, uint2 &NX_, uint32_t &NB_, uint32_t &NE_) {
-        const uint32_t st = st_of(i);
-        NX_ = rec[(ubase + st) * 64u + lane + vz];
-        NB_ = sbase[ubase + st + vz];
-        NE_ = sbase[ubase + st + 1u + vz];
-    };
-    auto load_b = [&](uint32_t i, u32x4 (&B_)[CT]) {
-        const uint32_t kr = k0 + st_of(i) * 32u;
-#pragma unroll
-        for (int c = 0; c < CT; c++) {
-            const uint32_t un = lane + 64u * c;
-            const uint32_t k = kr + un / UB, cu = (un % UB) * 8u;
-            if constexpr (DBG == 3) B_[c] = u32x4{k, cu, k, cu};
-            else B_[c] = *reinterpret_cast<const u32x4 *>(B + (size_t)(k < K ? k : K - 1u) * N + col0 + (cu < nv ? cu : 0u));
-        }
-    };
-    // the slot takes over the record it loaded a round ago, issues its step's values, and
-    // loads the record of its step a round ahead
-    auto load_v = [&](uint32_t i, uint2 &NX_, uint32_t &NB_, uint32_t &NE_, uint2 &RC_, uint32_t &RL_,
-                      u32x4 (&VR_)[NVB]) {
-        RC_ = NX_;
-        const uint32_t b0 = NB_ & ~7u, len = NE_ - b0;  // halves from the aligned start
-        RL_ = NB_ - b0;
-#pragma unroll
-        for (int j = 0; j < NVB; j++) {
-            const uint32_t h = 8u * (lane + 64u * j);
-            if constexpr (DBG == 2) VR_[j] = u32x4{RC_.x, RC_.y, RC_.x, RC_.y};
-            else VR_[j] = *reinterpret_cast<const u32x4 *>(vals + b0 + (h < len ? h : 0u));
-        }
-        load_rec(i + D, NX_, NB_, NE_);
-    };
-#pragma unroll
-    for (int d = 0; d < D; d++) load_rec((uint32_t)d, NX[d], NB[d], NE[d]);
-#pragma unroll
-    for (int d = 0; d < D; d++) load_b((uint32_t)d, BR[d]);
-#pragma unroll
-    for (int d = 0; d < D; d++) load_v((uint32_t)d, NX[d], NB[d], NE[d], RC[d], RL[d], VR[d]);
-    // the selector table (written by wave 0) before any wave expands a fragment
-    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __asm__ volatile("" ::: "memory");
-    GS_KB_STAMP(1u);
-
-    f4v acc[RT][CT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[rt][ct] = f4v{0.f, 0.f, 0.f, 0.f};
-
-    auto step = [&](uint32_t i, uint2 &NX_, uint32_t &NB_, uint32_t &NE_, uint2 &RC_, uint32_t &RL_,
-                    u32x4 (&VR_)[NVB], u32x4 (&B_)[CT]) {
-        const bool live = i < nsw;  // wave-uniform
-        h8v av[RT], bv[CT];
-        if (live) {
-            const uint32_t kr = k0 + (wv + i * W) * 32u;
-#pragma unroll
-            for (int c = 0; c < CT; c++) {
-                const uint32_t un = lane + 64u * c, k = un / UB, s = un % UB;
-                *reinterpret_cast<u32x4 *>(bst + k * RB + b_piece<CT>(k, s >> 1) * 32u + (s & 1u) * 16u) =
-                    kr + k < K && s * 8u < nv ? B_[c] : zero4;
-            }
-#pragma unroll
-            for (int j = 0; j < NVB; j++) *reinterpret_cast<u32x4 *>(vst + (lane + 64u * j) * 16u) = VR_[j];
-            const uint32_t kb = 8u * (lane >> 4);
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                s4v t2[2];
-#pragma unroll
-                for (int hh = 0; hh < 2; hh++) {
-                    const uint32_t k = kb + 4u * hh + ((lane & 15u) >> 2);
-                    t2[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (lds_s4v *)(bst + k * RB + b_piece<CT>(k, ct) * 32u + (lane & 3u) * 8u));
-                }
-                __builtin_memcpy(&bv[ct], t2, 16);
-            }
-            uint32_t p = RL_ + (RC_.y >> 16);
-#pragma unroll
-            for (int t = 0; t < RT; t++) {
-                const uint32_t m = mbyte(RC_, t);
-                const uint2 sl = lut[m & 15u], sh = lut[m >> 4];
-                const u32x2_a2 lo = *reinterpret_cast<const u32x2_a2 *>(vst + 2u * p);
-                const u32x2_a2 hi = *reinterpret_cast<const u32x2_a2 *>(vst + 2u * (p + __builtin_popcount(m & 15u)));
-                p += __builtin_popcount(m);
-                uint32_t w4[4];
-                w4[0] = __builtin_amdgcn_perm(lo.y, lo.x, sl.x);
-                w4[1] = __builtin_amdgcn_perm(lo.y, lo.x, sl.y);
-                w4[2] = __builtin_amdgcn_perm(hi.y, hi.x, sh.x);
-                w4[3] = __builtin_amdgcn_perm(hi.y, hi.x, sh.y);
-                __builtin_memcpy(&av[t], w4, 16);
-            }
-        }
-        load_b(i + D, B_);
-        load_v(i + D, NX_, NB_, NE_, RC_, RL_, VR_);
-        if (live) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[rt], bv[ct], acc[rt][ct], 0, 0, 0);
-            if (i < 16u) GS_KB_STAMP(3u + i);
-        }
-    };
-    const bool young = wv >= W / 2u;
-    if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(1);
-    for (uint32_t i0 = 0; i0 < nsw; i0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; d++) step(i0 + d, NX[d], NB[d], NE[d], RC[d], RL[d], VR[d], BR[d]);
-    }
-    if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(0);
-    GS_KB_STAMP(20u);
-    // ---- K-split ticket: wave 0 takes its row block's arrival ticket as soon as its own
-    // loop ends, so the add's round trip overlaps the partial-tile reduction below
-    uint32_t *arr = arrivals + (size_t)g * gridDim.y + blockIdx.y;
-    uint32_t ticket = 0;
-    if (S > 1 && wv == 0 && lane == 0) ticket = __hip_atomic_fetch_add(arr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // ---- wave partial tiles -> LDS (the trailing loads write registers only), summed in
-    // wave order.  Item t = (tile, lane) of a 16x16 tile: the 4 rows 4*(lane/16)+i of
-    // column lane%16.  When the W partial tiles fit LDS beside the wave images (APART), each
-    // wave stores its tile as soon as its loop ends, without waiting for the others
-    constexpr bool APART = kb_red_apart(CT, RT, W, NVB);
-    f4v *red = reinterpret_cast<f4v *>(lds + (APART ? kb_stage_bytes(CT, W, NVB) : 0u));
-    constexpr bool HALVES = !APART && ks_red_halves(CT, RT, W);
-    constexpr uint32_t WR = HALVES ? W / 2 : W;  // partial tiles summed from LDS
-    uint32_t *flag = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(red) + (size_t)WR * RT * CT * 1024u);
-    if constexpr (!APART) {
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-    }
-    if constexpr (HALVES) {
-        if (wv >= WR) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) red[(((wv - WR) * RT + rt) * CT + ct) * 64u + lane] = acc[rt][ct];
-        }
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-        if (wv < WR) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) acc[rt][ct] += red[((wv * RT + rt) * CT + ct) * 64u + lane];
-        }
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-    }
-    if (wv < WR) {
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) red[((wv * RT + rt) * CT + ct) * 64u + lane] = acc[rt][ct];
-    }
-    if (S > 1 && wv == 0 && lane == 0) *flag = ticket;  // (waits for the add's return)
-    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __asm__ volatile("" ::: "memory");
-    constexpr uint32_t NI = RT * CT * 64u, NT = 64u * W;
-    const uint32_t r0 = bmtb_first_row[g], R = bmtb_first_row[g + 1] - r0;
-    auto item_sum = [&](uint32_t t) {
-        f4v sum = red[t];
-#pragma unroll
-        for (uint32_t w = 1; w < WR; w++) sum += red[w * NI + t];
-        return sum;
-    };
-    auto store_item = [&](uint32_t t, const f4v &v) {
-        const uint32_t ln = t & 63u, tt = t >> 6, rt = tt / CT, ct = tt % CT;
-        const uint32_t col = 16u * ct + (ln & 15u), rb = 16u * rt + 4u * (ln >> 4);
-        if (col >= nv) return;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; i++)
-            if (rb + i < R) C[(size_t)(row_base + r0 + rb + i) * N + col0 + col] = (f16)v[i];
-    };
-    GS_KB_STAMP(21u);
-    if (S == 1) {
-        for (uint32_t t = tid; t < NI; t += NT) store_item(t, item_sum(t));
-        GS_KB_STAMP(22u);
-        return;
-    }
-    // ---- K-split combine by tagged slabs.  Every fp32 word of a published slab carries
-    // its own validity tag in the low mantissa bit (the reader drops the bit, a 2^-24
-    // relative truncation), so no store needs to be drained before a signal: every workgroup
-    // stores its slab with 16-B write-through (sc1) stores, and the one that drew the last
-    // ticket loads each other slab word with agent-scope (sc1) loads until its tag reads
-    // this launch's value -- its writer holds an earlier ticket, so it is running and its
-    // stores are issued or about to be -- sums the S partials in q order (deterministic) and
-    // writes C.  The tag alternates from launch to launch: the arrival counter holds
-    // (epoch << 16) | arrivals, the tag is epoch ^ 1, and the last workgroup re-arms the
-    // counter with the epoch flipped and no arrivals.  Every slab word then holds the
-    // previous launch's tag when a launch starts (the last workgroup stores its own slab
-    // too), and the zero-filled first state reads as "tag 0, epoch 0" -- so no slab is
-    // cleared after use ((S - 1) fewer slab stores than clearing, the last workgroup's own
-    // store issued before it waits).  Every access to the slabs is sc1 (MI355X_MICROARCH.md
-    // Workgroup dispatch, Valid forms: the R2 granule, here one naturally aligned word).
-    // The next launch on the stream starts after these stores complete.
-    const uint32_t tk = *flag & 0xffffu, tag = ((*flag >> 16) & 1u) ^ 1u;
-    f4v *slab = reinterpret_cast<f4v *>(slabs) + ((size_t)u * gridDim.y + blockIdx.y) * NI;
-    auto tagged = [&](const f4v &v) {
-        u32x4 w;
-        __builtin_memcpy(&w, &v, 16);
-        w[0] = (w[0] & ~1u) | tag; w[1] = (w[1] & ~1u) | tag; w[2] = (w[2] & ~1u) | tag; w[3] = (w[3] & ~1u) | tag;
-        return w;
-    };
-    for (uint32_t t = tid; t < NI; t += NT) {
-        const u32x4 w = tagged(item_sum(t));
-        __asm__ volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(slab + t), "v"(w) : "memory");
-    }
-    if (tk != S - 1u) {
-        GS_KB_STAMP(22u);
-        return;
-    }
-    if (tid == 0) __hip_atomic_store(arr, tag << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const f4v *base = reinterpret_cast<const f4v *>(slabs) + blockIdx.y * NI;
-    const size_t qstride = (size_t)gridDim.y * NI;  // slab of (g, qq) = base + (g*S + qq) * qstride
-    uint32_t *err = arrivals + (size_t)(nwg / S) * gridDim.y;  // the replica's device error word
-    for (uint32_t t = tid; t < NI; t += NT) {
-        f4v sum = {0.f, 0.f, 0.f, 0.f};
-        for (uint32_t qq = 0; qq < S; qq++) {
-            u32x4 w;
-            if (qq == q) {  // truncated as a published word is (whichever workgroup is last: deterministic)
-                w = tagged(item_sum(t));
-            } else {
-                w = ks_slab_wait(reinterpret_cast<const uint32_t *>(base + ((size_t)g * S + qq) * qstride + t), tag, err,
-                                 GS_KS_FORCE(prio));
-            }
-            w[0] &= ~1u; w[1] &= ~1u; w[2] &= ~1u; w[3] &= ~1u;
-            f4v x;
-            __builtin_memcpy(&x, &w, 16);
-            sum += x;
-        }
-        store_item(t, sum);
-    }
-    GS_KB_STAMP(22u);
-#undef GS_KB_STAMP
-}
-
-template <int CT, int RT, int W, int D, int NVB, bool STAMPS = false, int DBG = 0>
-__global__ __launch_bounds__(64 * W) void k_mfma_kb(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
-                                                    const uint2 *__restrict__ rec,       // (u*NS + step)*64 + lane
-                                                    const uint32_t *__restrict__ sbase,  // u*NS + step (+1)
-                                                    const f16 *__restrict__ vals, const f16 *__restrict__ B,
-                                                    f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
-                                                    uint32_t NS, uint32_t nwg, uint32_t row_base,
-                                                    float *__restrict__ slabs, uint32_t *__restrict__ arrivals,
-                                                    uint64_t *__restrict__ stamps = nullptr, uint32_t prio = 0) {
-    kb_body<CT, RT, W, D, NVB, STAMPS, DBG>(bmtb_first_row, rec, sbase, vals, B, C, K, N, S, NS, nwg, row_base, slabs, arrivals,
-                                  stamps, blockIdx.x, prio);
-}
-
-#ifdef GS_EXPERIMENTS  // opt-in, measured slower than k_mfma_rows / k_mfma_ks (make EXPERIMENTS=1)
-// ---------------------------------------------------------------------------
-// k_mfma_bm -- BMTB row blocks on the matrix cores from a bitmap layout, with the
-// dense A fragments built in registers (no dense image, no LDS scatter).
-// Why: k_mfma_rows / k_mfma_ks move 4 B per nonzero ([u16 position][f16 value]) and
-// scatter every entry into a dense LDS image (two LDS stores per entry, one to clear
-// it); at 30% density a bitmap costs 0.42 B per nonzero, so A is ~2.4 B per nonzero
-// and no entry ever passes through LDS.
-// Layout (host/device_layout.cc build_bm_tiles): unit u = (row block g, K range q) of
-// NS 32-column k-steps; per (u, step) one 8-byte record per lane l: byte t (t < RT) is
-// the occupancy of row 16t + l%16, columns 32*step + 8*(l/16) + [0, 8) -- exactly the 8
-// halves lane l holds of the A operand of v_mfma_f32_16x16x32_f16 for row tile t --
-// and bytes 6..7 the lane's first value (halves, from the step's base sbase[u*NS+step]);
-// a step's values are stored lane after lane, tile after tile, ascending columns.
-// Wave w of the workgroup owns the range's k-steps w, w+W, ...: per k-step it loads the
-// 32 B rows into registers and stores them into its own LDS ring slot (32-B pieces
-// permuted by b_piece, so the ds_read_b64_tr_b16 fragment reads are conflict-free; not
-// LDS-DMA: the compiler then waits for every DMA in flight before each LDS read of the
-// same wave), loads the record, then per row tile two 8-byte
-// value windows (at the tile's first value and past the low nibble's values; 2-byte
-// aligned loads) that two v_perm_b32 each expand into the tile's dense fragment with
-// selectors from a 16-entry table in LDS, and runs RT x CT MFMAs.  Pipeline per wave:
-// B + record two steps ahead, B store + values one step ahead (counted waits); no
-// workgroup barrier until the end.  Epilogue as k_mfma_ks: the W partial tiles summed in
-// wave order through LDS, then C (S = 1) or a write-through fp32 slab + one arrival add,
-// the last of the row block's S workgroups summing the slabs in q order (deterministic).
-// Rows of B past K are read as row K-1 against zero A columns (a non-finite B value
-// there gives NaN: the documented matrix-core deviation).
-// ---------------------------------------------------------------------------
-
-// STAMPS (diagnostic build only, gs_debug_mfma_timeline): lane 0 of every wave records
-// s_memtime into stamps[(workgroup * W + wave) * 16 + slot]: 0 start, 1 B + records issued,
-// 2 values issued, 3 B stored (all landed), 4 MFMAs done (first batch), 5 loop done,
-// 6 reduced, 7 slab published, 8 end
-template <int CT, int RT, int W, int NBT, bool STAMPS = false>
-__global__ __launch_bounds__(64 * W) void k_mfma_bm(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
-                                                    const uint2 *__restrict__ rec,       // (u*NS + step)*64 + lane
-                                                    const uint32_t *__restrict__ sbase,  // u*NS + step (+1)
-                                                    const f16 *__restrict__ vals, const f16 *__restrict__ B,
-                                                    f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
-                                                    uint32_t NS, uint32_t nwg, uint32_t row_base,
-                                                    float *__restrict__ slabs, uint32_t *__restrict__ arrivals,
-                                                    uint64_t *__restrict__ stamps = nullptr) {
-    static_assert(RT >= 1 && RT <= 6, "six mask bytes per record");
-#define GS_BM_STAMP(slot)                                                                          \
-    if constexpr (STAMPS) {                                                                        \
-        if ((threadIdx.x & 63u) == 0) stamps[((size_t)blockIdx.x * W + (threadIdx.x >> 6)) * 16u + (slot)] = __builtin_amdgcn_s_memtime(); \
-    }
-    GS_BM_STAMP(0u);
-    constexpr uint32_t RB = 32 * CT;     // bytes per LDS B row (a 16*CT-column tile)
-    constexpr uint32_t UB = 2 * CT;      // 16-B units per B row
-    constexpr uint32_t STG = 32u * RB;   // one k-step of B rows = CT LDS-DMA wave-instructions
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t u = xcd_block(blockIdx.x, nwg);  // nwg == gridDim.x
-    const uint32_t g = u / S, q = u - g * S;
-    const uint32_t col0 = blockIdx.y * 16u * CT, nv = min(16u * CT, N - col0);
-    uint2 *lut = reinterpret_cast<uint2 *>(lds);
-    unsigned char *ring = lds + 128u + wv * NBT * STG;  // this wave's NBT k-step slots
-    if (tid < 16u) lut[tid] = make_uint2(bm_sel(tid, 0), bm_sel(tid, 1));
-    const uint32_t k0 = q * NS * 32u;
-    const uint32_t nsw = NS > wv ? (NS - wv + W - 1u) / W : 0u;  // this wave's k-steps
-    const size_t ub = (size_t)u * NS;
-    // steps past the wave's last re-read its first (cached)
-    auto step_of = [&](uint32_t i) -> uint32_t { return i < nsw ? wv + i * W : wv; };
-    // B rows of step i -> registers (16-B units, lane-linear over the step's 32 rows), then into
-    // slot j with the 32-B pieces permuted by b_piece (conflict-free transposed reads).  Not
-    // LDS-DMA: the compiler then waits for all DMA in flight before the wave's next
-    // dependent load, which serialises the records and the value windows behind the B rows
-    auto load_b = [&](uint32_t i, u32x4 (&BR)[CT]) {
-        const uint32_t kr = k0 + step_of(i) * 32u;
-#pragma unroll
-        for (uint32_t c = 0; c < CT; c++) {
-            const uint32_t un = c * 64u + lane, k = un / UB, cu = (un % UB) * 8u;
-            const uint32_t kk = kr + k < K ? kr + k : K - 1u;
-            BR[c] = *reinterpret_cast<const u32x4 *>(B + (size_t)kk * N + col0 + (cu < nv ? cu : 0u));
-        }
-    };
-    auto store_b = [&](uint32_t j, const u32x4 (&BR)[CT]) {
-        unsigned char *dst = ring + j * STG;
-#pragma unroll
-        for (uint32_t c = 0; c < CT; c++) {
-            const uint32_t un = c * 64u + lane, k = un / UB, s = un % UB;
-            *reinterpret_cast<u32x4 *>(dst + k * RB + b_piece<CT>(k, s >> 1) * 32u + (s & 1u) * 16u) = BR[c];
-        }
-    };
-    auto mbyte = [](const uint2 &r, int t) -> uint32_t {
-        return t < 4 ? (r.x >> (8 * t)) & 0xffu : (r.y >> (8 * (t - 4))) & 0xffu;
-    };
-    f4v acc[RT][CT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[rt][ct] = f4v{0.f, 0.f, 0.f, 0.f};
-    const uint32_t kb = 8u * (lane >> 4);
-    bool first = true;
-    // batches of NBT k-steps: every load of the batch in flight at once (records, then the B
-    // rows by DMA, then -- once each record is in -- the value windows), then the MFMAs
-    for (uint32_t i0 = 0; i0 < nsw; i0 += NBT) {
-        // B rows first (L2-served: they return before the records from HBM, and loads retire
-        // in order, so waiting for the records costs nothing extra)
-        u32x4 br[NBT][CT];
-#pragma unroll
-        for (int j = 0; j < NBT; j++) load_b(i0 + j, br[j]);
-        uint2 rc[NBT];
-        uint32_t sb[NBT];
-#pragma unroll
-        for (int j = 0; j < NBT; j++) {
-            sb[j] = sbase[ub + step_of(i0 + j)];  // wave-uniform: a scalar load
-            rc[j] = rec[(ub + step_of(i0 + j)) * 64u + lane];
-        }
-        if (first) GS_BM_STAMP(1u);
-        u32x2_a2 vv[NBT][RT][2];
-#pragma unroll
-        for (int j = 0; j < NBT; j++) {
-            uint32_t p = sb[j] + (rc[j].y >> 16);
-#pragma unroll
-            for (int t = 0; t < RT; t++) {
-                const uint32_t m = mbyte(rc[j], t);
-                vv[j][t][0] = *reinterpret_cast<const u32x2_a2 *>(vals + p);
-                vv[j][t][1] = *reinterpret_cast<const u32x2_a2 *>(vals + p + __builtin_popcount(m & 15u));
-                p += __builtin_popcount(m);
-            }
-        }
-        if (first) GS_BM_STAMP(2u);
-#pragma unroll
-        for (int j = 0; j < NBT; j++) store_b(j, br[j]);
-        if (first) {  // the selector table (its stores, once)
-            __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __asm__ volatile("" ::: "memory");
-            GS_BM_STAMP(3u);
-        }
-#pragma unroll
-        for (int j = 0; j < NBT; j++) {
-            if (i0 + j < nsw) {
-                const unsigned char *bst = ring + j * STG;
-                h8v bv[CT];
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) {
-                    s4v t2[2];
-#pragma unroll
-                    for (int hh = 0; hh < 2; hh++) {
-                        const uint32_t k = kb + 4u * hh + ((lane & 15u) >> 2);
-                        t2[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (lds_s4v *)(bst + k * RB + b_piece<CT>(k, ct) * 32u + (lane & 3u) * 8u));
-                    }
-                    __builtin_memcpy(&bv[ct], t2, 16);
-                }
-#pragma unroll
-                for (int t = 0; t < RT; t++) {
-                    const uint32_t m = mbyte(rc[j], t);
-                    const uint2 sl = lut[m & 15u], sh = lut[m >> 4];
-                    const u32x2_a2 lo = vv[j][t][0], hi = vv[j][t][1];
-                    uint32_t w[4];
-                    w[0] = __builtin_amdgcn_perm(lo.y, lo.x, sl.x);
-                    w[1] = __builtin_amdgcn_perm(lo.y, lo.x, sl.y);
-                    w[2] = __builtin_amdgcn_perm(hi.y, hi.x, sh.x);
-                    w[3] = __builtin_amdgcn_perm(hi.y, hi.x, sh.y);
-                    h8v a;
-                    __builtin_memcpy(&a, w, 16);
-#pragma unroll
-                    for (int ct = 0; ct < CT; ct++)
-                        acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bv[ct], acc[t][ct], 0, 0, 0);
-                }
-            }
-        }
-        if (first) {
-            GS_BM_STAMP(4u);
-            first = false;
-        }
-    }
-    GS_BM_STAMP(5u);
-    if (first) {  // a wave with no k-steps still meets the table barrier
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-    }
-    // every wave is done with its ring before it is reused for the partial tiles
-    __syncthreads();
-    f4v *red = reinterpret_cast<f4v *>(lds);
-    constexpr bool HALVES = bm_red_halves(CT, RT, W);
-    constexpr uint32_t WR = HALVES ? W / 2 : W;
-    if constexpr (HALVES) {
-        if (wv >= WR) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) red[(((wv - WR) * RT + rt) * CT + ct) * 64u + lane] = acc[rt][ct];
-        }
-        __syncthreads();
-        if (wv < WR) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) acc[rt][ct] += red[((wv * RT + rt) * CT + ct) * 64u + lane];
-        }
-        __syncthreads();
-    }
-    if (wv < WR) {
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) red[((wv * RT + rt) * CT + ct) * 64u + lane] = acc[rt][ct];
-    }
-    __syncthreads();
-    constexpr uint32_t NI = RT * CT * 64u, NT = 64u * W;
-    const uint32_t r0 = bmtb_first_row[g], R = bmtb_first_row[g + 1] - r0;
-    auto item_sum = [&](uint32_t t) {
-        f4v sum = red[t];
-#pragma unroll
-        for (uint32_t w = 1; w < WR; w++) sum += red[w * NI + t];
-        return sum;
-    };
-    auto store_item = [&](uint32_t t, const f4v &v) {
-        const uint32_t ln = t & 63u, tt = t >> 6, rt = tt / CT, ct = tt % CT;
-        const uint32_t col = 16u * ct + (ln & 15u), rb = 16u * rt + 4u * (ln >> 4);
-        if (col >= nv) return;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; i++)
-            if (rb + i < R) C[(size_t)(row_base + r0 + rb + i) * N + col0 + col] = (f16)v[i];
-    };
-    GS_BM_STAMP(6u);
-    if (S == 1) {
-        for (uint32_t t = tid; t < NI; t += NT) store_item(t, item_sum(t));
-        GS_BM_STAMP(8u);
-        return;
-    }
-    // K-split hand-off (k_mfma_ks's form): 16-B write-through slab stores, every storing
-    // wave's vmcnt(0), a barrier, one agent-scope arrival add; the last adder (told by the
-    // returned count) loads the other slabs with agent-scope (sc1) loads
-    f4v *slab = reinterpret_cast<f4v *>(slabs) + ((size_t)u * gridDim.y + blockIdx.y) * NI;
-    for (uint32_t t = tid; t < NI; t += NT) {
-        const f4v v = item_sum(t);
-        __asm__ volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(slab + t), "v"(v) : "memory");
-    }
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    uint32_t *flag = reinterpret_cast<uint32_t *>(lds + (size_t)WR * NI * 16u);
-    uint32_t *arr = arrivals + (size_t)g * gridDim.y + blockIdx.y;
-    if (tid == 0) *flag = __hip_atomic_fetch_add(arr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    GS_BM_STAMP(7u);
-    if (*flag != S - 1u) {
-        GS_BM_STAMP(8u);
-        return;
-    }
-    if (tid == 0) __hip_atomic_store(arr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const f4v *base = reinterpret_cast<const f4v *>(slabs) + blockIdx.y * NI;
-    const size_t qstride = (size_t)gridDim.y * NI;
-    for (uint32_t t = tid; t < NI; t += NT) {
-        const f4v own = item_sum(t);
-        f4v sum = {0.f, 0.f, 0.f, 0.f};
-        for (uint32_t qq = 0; qq < S; qq++) {
-            if (qq == q) {
-                sum += own;
-                continue;
-            }
-            const float *src = reinterpret_cast<const float *>(base + ((size_t)g * S + qq) * qstride + t);
-            f4v x;
-#pragma unroll
-            for (int i = 0; i < 4; i++) x[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sum += x;
-        }
-        store_item(t, sum);
-    }
-    GS_BM_STAMP(8u);
-#undef GS_BM_STAMP
-}
-
-// ---------------------------------------------------------------------------
-// k_mfma_bm2 -- k_mfma_bm's layout with one wave per 16-row tile (RT waves per
-// workgroup): no cross-wave reduction, and every wave streams its tile's records and
-// value windows through register rings (records 16 k-steps ahead, values 8 ahead) while
-// the workgroup's B slice (NS k-steps, staged once by all waves, one barrier) stays in
-// LDS.  K split: each wave publishes its 16 x N fp32 tile (8-B agent-scope stores), one
-// agent-scope add per (row block, tile), the last adder sums the slabs in K-range order
-// (deterministic) and stores C.
-// ---------------------------------------------------------------------------
-template <int CT, int RT>
-__global__ __launch_bounds__(64 * RT) void k_mfma_bm2(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
-                                                     const uint2 *__restrict__ rec, const uint32_t *__restrict__ sbase,
-                                                     const f16 *__restrict__ vals, const f16 *__restrict__ B,
-                                                     f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
-                                                     uint32_t NS, uint32_t nwg, uint32_t row_base,
-                                                     float *__restrict__ slabs, uint32_t *__restrict__ arrivals) {
-    constexpr uint32_t RB = 32 * CT, UB = 2 * CT, STG = 32u * RB;
-    constexpr uint32_t DR = 16, DV = 8;  // look-ahead of the records / value windows (k-steps)
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // = this wave's row tile
-    const uint32_t u = xcd_block(blockIdx.x, nwg);
-    const uint32_t g = u / S, q = u - g * S;
-    const uint32_t col0 = blockIdx.y * 16u * CT, nv = min(16u * CT, N - col0);
-    uint2 *lut = reinterpret_cast<uint2 *>(lds);
-    unsigned char *bsl = lds + 128u;  // NS k-steps of B rows
-    if (tid < 16u) lut[tid] = make_uint2(bm_sel(tid, 0), bm_sel(tid, 1));
-    const uint32_t k0 = q * NS * 32u;
-    const size_t ub = (size_t)u * NS;
-    const uint32_t tsh = 8u * (wv & 3u);  // this tile's mask byte in the record word
-    auto mask_of = [&](const uint2 &r) -> uint32_t { return ((wv < 4u ? r.x : r.y) >> tsh) & 0xffu; };
-    // the value offset of this lane's run for this tile: the record's lane offset + the
-    // values of the lower tiles (bytes below this tile's)
-    auto vstart = [&](const uint2 &r, uint32_t sb) -> uint32_t {
-        uint32_t lower = wv < 4u ? (wv ? r.x & ((1u << (8u * wv)) - 1u) : 0u)
-                                 : r.x;
-        uint32_t p = sb + (r.y >> 16) + (uint32_t)__builtin_popcount(lower);
-        if (wv >= 4u) p += (uint32_t)__builtin_popcount(r.y & ((1u << (8u * (wv - 4u))) - 1u) & 0xffffu);
-        return p;
-    };
-    auto ld_rec = [&](uint32_t s, uint32_t &sb) -> uint2 {
-        const uint32_t ss = s < NS ? s : NS - 1u;
-        sb = sbase[ub + ss];
-        return rec[(ub + ss) * 64u + lane];
-    };
-    auto ld_vals = [&](const uint2 &r, uint32_t sb, u32x2_a2 (&V)[2]) {
-        const uint32_t p = vstart(r, sb), m = mask_of(r);
-        V[0] = *reinterpret_cast<const u32x2_a2 *>(vals + p);
-        V[1] = *reinterpret_cast<const u32x2_a2 *>(vals + p + __builtin_popcount(m & 15u));
-    };
-    // records of the first DR steps (the critical HBM chain) before the B slice
-    uint2 rr[DR];
-    uint32_t rs[DR];
-#pragma unroll
-    for (uint32_t j = 0; j < DR; j++) rr[j] = ld_rec(j, rs[j]);
-    // B slice: step s staged by wave s % RT (registers -> ds_write_b128, b_piece permutation)
-    for (uint32_t s = wv; s < NS; s += RT) {
-        const uint32_t kr = k0 + s * 32u;
-        u32x4 br[CT];
-#pragma unroll
-        for (uint32_t c = 0; c < CT; c++) {
-            const uint32_t un = c * 64u + lane, k = un / UB, cu = (un % UB) * 8u;
-            const uint32_t kk = kr + k < K ? kr + k : K - 1u;
-            br[c] = *reinterpret_cast<const u32x4 *>(B + (size_t)kk * N + col0 + (cu < nv ? cu : 0u));
-        }
-#pragma unroll
-        for (uint32_t c = 0; c < CT; c++) {
-            const uint32_t un = c * 64u + lane, k = un / UB, sx = un % UB;
-            *reinterpret_cast<u32x4 *>(bsl + s * STG + k * RB + b_piece<CT>(k, sx >> 1) * 32u + (sx & 1u) * 16u) = br[c];
-        }
-    }
-    // the value windows of the first DV steps
-    u32x2_a2 vv[DV][2];
-#pragma unroll
-    for (uint32_t j = 0; j < DV; j++) ld_vals(rr[j], rs[j], vv[j]);
-    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // the B slice and the selector table
-    __asm__ volatile("" ::: "memory");
-    f4v acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) acc[ct] = f4v{0.f, 0.f, 0.f, 0.f};
-    const uint32_t kb = 8u * (lane >> 4);
-    // step i (ring slots i % DR, i % DV): compute i, then refill: values of i + DV (their
-    // record is in slot (i + DV) % DR), record of i + DR
-    for (uint32_t i0 = 0; i0 < NS; i0 += DR) {
-#pragma unroll
-        for (uint32_t d = 0; d < DR; d++) {
-            const uint32_t i = i0 + d;
-            if (i < NS) {
-                const unsigned char *bst = bsl + i * STG;
-                const uint32_t m = mask_of(rr[d]);
-                const uint2 sl = lut[m & 15u], sh = lut[m >> 4];
-                const u32x2_a2 lo = vv[d % DV][0], hi = vv[d % DV][1];
-                uint32_t w[4];
-                w[0] = __builtin_amdgcn_perm(lo.y, lo.x, sl.x);
-                w[1] = __builtin_amdgcn_perm(lo.y, lo.x, sl.y);
-                w[2] = __builtin_amdgcn_perm(hi.y, hi.x, sh.x);
-                w[3] = __builtin_amdgcn_perm(hi.y, hi.x, sh.y);
-                h8v a;
-                __builtin_memcpy(&a, w, 16);
-#pragma unroll
-                for (int ct = 0; ct < CT; ct++) {
-                    s4v t2[2];
-#pragma unroll
-                    for (int hh = 0; hh < 2; hh++) {
-                        const uint32_t k = kb + 4u * hh + ((lane & 15u) >> 2);
-                        t2[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (lds_s4v *)(bst + k * RB + b_piece<CT>(k, ct) * 32u + (lane & 3u) * 8u));
-                    }
-                    h8v bv;
-                    __builtin_memcpy(&bv, t2, 16);
-                    acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bv, acc[ct], 0, 0, 0);
-                }
-            }
-            // refill (past NS: re-reads of the last step, never used)
-            ld_vals(rr[(d + DV) % DR], rs[(d + DV) % DR], vv[d % DV]);
-            rr[d] = ld_rec(i + DR, rs[d]);
-        }
-    }
-    const uint32_t r0 = bmtb_first_row[g], R = bmtb_first_row[g + 1] - r0;
-    auto store_tile = [&](const f4v (&v)[CT]) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
-            const uint32_t col = 16u * ct + (lane & 15u);
-            if (col >= nv) continue;
-#pragma unroll
-            for (uint32_t e = 0; e < 4; e++) {
-                const uint32_t rw = 16u * wv + 4u * (lane >> 4) + e;
-                if (rw < R) C[(size_t)(row_base + r0 + rw) * N + col0 + col] = (f16)v[ct][e];
-            }
-        }
-    };
-    if (S == 1) {
-        store_tile(acc);
-        return;
-    }
-    if (16u * wv >= R) return;  // a tile past the block's rows: no counter traffic
-    // K split hand-off per (row block, tile, column tile)
-    constexpr uint32_t TI = CT * 64u;
-    const size_t tix = ((size_t)g * gridDim.y + blockIdx.y) * RT + wv;
-    f4v *slab = reinterpret_cast<f4v *>(slabs) + (tix * S + q) * TI;
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) {
-        uint64_t *dst = reinterpret_cast<uint64_t *>(slab + ct * 64u + lane);
-        uint64_t w[2];
-        __builtin_memcpy(w, &acc[ct], 16);
-        __hip_atomic_store(dst, w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(dst + 1, w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    uint32_t old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(&arrivals[tix], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    old = __builtin_amdgcn_readfirstlane(old);
-    if (old != S - 1u) return;
-    if (lane == 0) __hip_atomic_store(&arrivals[tix], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    f4v sum[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) sum[ct] = f4v{0.f, 0.f, 0.f, 0.f};
-    const f4v *base = reinterpret_cast<const f4v *>(slabs) + tix * S * TI;
-    for (uint32_t qq = 0; qq < S; qq++) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
-            if (qq == q) {
-                sum[ct] += acc[ct];
-            } else {
-                const uint64_t *src = reinterpret_cast<const uint64_t *>(base + (size_t)qq * TI + ct * 64u + lane);
-                uint64_t w[2];
-                w[0] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                w[1] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                f4v x;
-                __builtin_memcpy(&x, w, 16);
-                sum[ct] += x;
-            }
-        }
-    }
-    store_tile(sum);
-}
-
-#endif  // GS_EXPERIMENTS (k_mfma_bm, k_mfma_bm2)
-// ---------------------------------------------------------------------------
 // k_nm_mfma -- fixed_interval_col_direction BMTs that are 2:4 panels
 //  on the sparse matrix cores:
 // v_smfmac_f32_16x16x64_f16 multiplies a 16x64 A tile stored as 16x32 values
@@ -3313,7 +1861,6 @@ __global__ __launch_bounds__(64 * RT) void k_mfma_bm2(const uint32_t *__restrict
 // prefetches in flight.  The four k-phase partial tiles are summed in a fixed
 // order through LDS ((q0 + q2) + (q1 + q3): deterministic) and stored as fp16.
 // ---------------------------------------------------------------------------
-typedef _Float16 h16v __attribute__((ext_vector_type(16)));
 // kNmWaves, kNmBlockBytes, kNmKC: kernel_consts.hpp
 
 // DBG (diagnostic builds only, GS_NM_DEBUG): 1 = no B loads in the loop, 2 = no A loads,
@@ -3555,465 +2102,6 @@ __global__ __launch_bounds__(64 * kNmWaves) void k_nm_mfma(const unsigned char *
     }
 }
 
-#ifdef GS_EXPERIMENTS  // opt-in, measured slower than k_nm_mfma (make EXPERIMENTS=1)
-// ---------------------------------------------------------------------------
-// k_nm_mfma_ks -- the same 2:4 panels (same HBM blocks as k_nm_mfma) with one 64-row
-// group per wave, four waves = 256 rows per workgroup and K split over `nsplit`
-// workgroups (config C3, N = 128).
-// Why: a k_nm_mfma workgroup (128 rows) streams all of B (1.8 MB at N = 128) for its
-// 1.0 MB of A, and one CU takes in only ~45-70 GB/s, so B is 64% of every CU's intake
-// (C3 runs at 69% of HBM at N = 32 and 40% at N = 128, profiles/r03_n_sweep.json).  Here a
-// workgroup owns 256 rows over half of K: B 0.9 MB + A 1.0 MB per CU (-32%).
-// One wave per SIMD: each wave holds its 64 x N fp32 tile (4 x CT accumulators, 128
-// registers at N = 128, the rest of the 512-register budget for the look-ahead), the A
-// blocks of the next 256-column chunk (four k-steps) in registers while it computes the
-// current one, and the B chunk is staged through registers by all 256 threads into a
-// double-buffered LDS image (b_piece permutation, one raw s_barrier per chunk: global
-// loads stay in flight across it).  No cross-wave reduction: every wave owns its rows.
-// K split: each wave publishes its fp32 tile (8-B agent-scope stores, its own vmcnt(0),
-// then one agent-scope add on its row group's counter); the wave whose add completes the
-// count sums the slabs in split order with agent-scope loads and stores C
-// (deterministic), then re-arms the counter.
-// ---------------------------------------------------------------------------
-template <int CT>
-__global__ __launch_bounds__(256) void k_nm_mfma_ks(const unsigned char *__restrict__ A,
-                                                   const f16 *__restrict__ B, f16 *__restrict__ C, uint32_t K,
-                                                   uint32_t S, uint32_t rows, uint32_t row_base, uint32_t nsplit,
-                                                   uint32_t ncs, float *__restrict__ slabs,
-                                                   uint32_t *__restrict__ arrivals) {
-    constexpr uint32_t N = 16 * CT, RB = 32 * CT, UB = 2 * CT;
-    constexpr uint32_t szB = kNmKC * RB;
-    constexpr uint32_t NTH = 256;
-    constexpr uint32_t NBU = szB / 16 / NTH;  // 16-B units of B per thread per chunk
-    constexpr uint32_t RPU = NTH / UB;        // B rows between a thread's units
-    static_assert(szB % (16 * NTH) == 0 && NTH % UB == 0, "whole B units per thread");
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t g = blockIdx.x / nsplit, sp = blockIdx.x - g * nsplit;
-    const uint32_t rg = g * 4u + wv;  // this wave's 64-row group
-    const uint32_t nch = S / 4u;
-    const uint32_t c0 = sp * ncs, ncl = min(nch, c0 + ncs) - c0;  // this workgroup's chunks
-    const unsigned char *arow = A + (size_t)rg * S * kNmBlockBytes;
-    const unsigned char *bbase = reinterpret_cast<const unsigned char *>(B);
-    const uint32_t bk = tid / UB, boff = bk * RB + (tid % UB) * 16u;  // this thread's first unit
-    auto bdst = [&](uint32_t i) {
-        const uint32_t k = bk + i * RPU, s = tid % UB;
-        return k * RB + b_piece<CT>(k, s >> 1) * 32u + (s & 1u) * 16u;
-    };
-    // the four k-step blocks of chunk c (clamped: past the range re-reads the last)
-    auto aload = [&](uint32_t i, u32x4 (&V)[4][4], uint2 (&I)[4]) {
-        const uint32_t c = c0 + min(i, ncl - 1u);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const unsigned char *blk = arow + (size_t)(4u * c + q) * kNmBlockBytes;
-            I[q] = *reinterpret_cast<const uint2 *>(blk + lane * 8u);
-#pragma unroll
-            for (int rt = 0; rt < 4; rt++) V[q][rt] = *reinterpret_cast<const u32x4 *>(blk + 512u + rt * 1024u + lane * 16u);
-        }
-    };
-    u32x4 bs[NBU];
-    auto bload = [&](uint32_t i) {
-        const uint32_t k0 = (c0 + min(i, ncl - 1u)) * kNmKC;
-        if (k0 + kNmKC <= K) {
-            const unsigned char *src = bbase + (size_t)k0 * RB;
-#pragma unroll
-            for (uint32_t u = 0; u < NBU; u++) bs[u] = *reinterpret_cast<const u32x4 *>(src + u * RPU * RB + boff);
-        } else {
-#pragma unroll
-            for (uint32_t u = 0; u < NBU; u++) {
-                const uint32_t kk = min(k0 + bk + u * RPU, K - 1u);
-                bs[u] = *reinterpret_cast<const u32x4 *>(bbase + (size_t)kk * RB + (tid % UB) * 16u);
-            }
-        }
-    };
-    auto bstore = [&](uint32_t i) {
-        const uint32_t k0 = (c0 + min(i, ncl - 1u)) * kNmKC;
-        unsigned char *lb = lds + (i & 1u) * szB;
-        if (k0 + kNmKC <= K) {
-#pragma unroll
-            for (uint32_t u = 0; u < NBU; u++) *reinterpret_cast<u32x4 *>(lb + bdst(u)) = bs[u];
-        } else {  // rows past K: zeros
-#pragma unroll
-            for (uint32_t u = 0; u < NBU; u++) {
-                const uint32_t z = k0 + bk + u * RPU < K ? ~0u : 0u;
-                *reinterpret_cast<u32x4 *>(lb + bdst(u)) = bs[u] & z;
-            }
-        }
-    };
-    f4v acc[4][CT];
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[rt][ct] = f4v{0.f, 0.f, 0.f, 0.f};
-    const uint32_t kl0 = 8u * (lane >> 4) + ((lane & 15u) >> 2);
-    auto compute = [&](uint32_t i, const u32x4 (&V)[4][4], const uint2 (&I)[4]) {
-        const unsigned char *lb = lds + (i & 1u) * szB;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            h8v av[4];
-#pragma unroll
-            for (int rt = 0; rt < 4; rt++) __builtin_memcpy(&av[rt], &V[q][rt], 16);
-            const int ix0 = (int)I[q].x, ix1 = (int)I[q].y;
-            const uint32_t kl = 64u * q + kl0;
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                s4v t[4];
-#pragma unroll
-                for (int h = 0; h < 4; h++) {
-                    const uint32_t k = kl + 32u * (h >> 1) + 4u * (h & 1);
-                    t[h] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (lds_s4v *)(lb + k * RB + b_piece<CT>(k, ct) * 32u + (lane & 3u) * 8u));
-                }
-                h16v b;
-                __builtin_memcpy(&b, t, 32);
-                acc[0][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av[0], b, acc[0][ct], ix0, 0, 0);
-                acc[1][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av[1], b, acc[1][ct], ix0, 0, 1);
-                acc[2][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av[2], b, acc[2][ct], ix1, 0, 0);
-                acc[3][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av[3], b, acc[3][ct], ix1, 0, 1);
-            }
-        }
-    };
-    // LDS stores of this thread done, then a raw barrier (the look-ahead loads stay in flight)
-    auto barrier = [&]() {
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __asm__ volatile("" ::: "memory");
-    };
-    u32x4 va[4][4], vb[4][4];
-    uint2 ia[4], ib[4];
-    aload(0, va, ia);
-    bload(0);
-    bstore(0);
-    barrier();
-    // chunk i: B of i+1 and A of i+1 in flight while i computes; B of i+1 staged after it
-    uint32_t i = 0;
-    // (sched_barriers keep the look-ahead loads in front of the MFMAs: the scheduler would
-    // otherwise sink them past the compute to shorten register lifetimes)
-    for (; i + 1 < ncl; i += 2) {
-        bload(i + 1);
-        aload(i + 1, vb, ib);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(i, va, ia);
-        __builtin_amdgcn_sched_barrier(0);
-        bstore(i + 1);
-        barrier();
-        bload(i + 2);
-        aload(i + 2, va, ia);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(i + 1, vb, ib);
-        __builtin_amdgcn_sched_barrier(0);
-        bstore(i + 2);
-        barrier();
-    }
-    if (i < ncl) compute(i, va, ia);
-    // the trailing look-ahead loads land in registers only
-    const bool live = rg * 64u < rows;
-    auto store_tile = [&](const f4v (&v)[4][CT]) {
-#pragma unroll
-        for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const uint32_t r = rg * 64u + rt * 16u + 4u * (lane >> 4) + e;
-                    if (r < rows) C[(size_t)(row_base + r) * N + ct * 16u + (lane & 15u)] = (f16)v[rt][ct][e];
-                }
-    };
-    if (nsplit == 1) {
-        if (live) store_tile(acc);
-        return;
-    }
-    if (!live) return;  // a row group past the matrix has no counter traffic
-    // K split: this wave's tile -> its slab (8-B agent-scope stores: write-through, and
-    // compiler-visible, so the MFMA-result -> store wait states are inserted -- an inline-asm
-    // 16-B store of the accumulators read one register before the smfmac had written it),
-    // then one add
-    constexpr uint32_t TI = 4u * CT * 64u;  // f4v per wave tile
-    f4v *slab = reinterpret_cast<f4v *>(slabs) + ((size_t)rg * nsplit + sp) * TI;
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
-            uint64_t *dst = reinterpret_cast<uint64_t *>(slab + (rt * CT + ct) * 64u + lane);
-            uint64_t w[2];
-            __builtin_memcpy(w, &acc[rt][ct], 16);
-            __hip_atomic_store(dst, w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(dst + 1, w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    uint32_t old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(&arrivals[rg], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    old = __builtin_amdgcn_readfirstlane(old);
-    if (old != nsplit - 1u) return;
-    if (lane == 0) __hip_atomic_store(&arrivals[rg], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const f4v *base = reinterpret_cast<const f4v *>(slabs) + (size_t)rg * nsplit * TI;
-    f4v sum[4][CT];
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) sum[rt][ct] = f4v{0.f, 0.f, 0.f, 0.f};
-    for (uint32_t qq = 0; qq < nsplit; qq++) {
-#pragma unroll
-        for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                if (qq == sp) {
-                    sum[rt][ct] += acc[rt][ct];
-                } else {
-                    const uint64_t *src = reinterpret_cast<const uint64_t *>(base + (size_t)qq * TI + (rt * CT + ct) * 64u + lane);
-                    uint64_t w[2];
-                    w[0] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    w[1] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    f4v x;
-                    __builtin_memcpy(&x, w, 16);
-                    sum[rt][ct] += x;
-                }
-            }
-    }
-    store_tile(sum);
-}
-
-#endif  // GS_EXPERIMENTS (k_nm_mfma_ks)
-
-// ---------------------------------------------------------------------------
-// k_nm_mfma4 -- the same 2:4 panels (build_nm_panels blocks) for wide B (N = 128, CT = 8),
-// with a quarter of k_nm_mfma's B bytes per row.
-// Why: a k_nm_mfma workgroup (128 rows, all of K) takes in 1.8 MB of B for its 1.0 MB of A,
-// and one CU's intake is the sum of its A (HBM, ~24 GB/s per CU) and B (L2, ~70 GB/s)
-// streams (DESIGN §4 model: 43 + 26 us on C3).  Here a workgroup owns 256 rows (four 64-row
-// groups) over one of S K ranges: B per CU halves (0.9 MB at S = 2), A per CU is unchanged,
-// the grid stays 224 workgroups on C3.
-// Waves: 8 = four row groups x two k-phases; wave (rh, q) takes k-steps 4c+q and 4c+q+2 of
-// every 256-row chunk c of its range (its 64 x 128 fp32 tile: 128 accumulator registers).
-// B chunks go to LDS by LDS-DMA (global_load_lds_dwordx4: no register staging, no LDS store
-// cycles; b_piece's XOR rides on the source address), two 64 KB buffers, one chunk ahead;
-// A blocks two chunks ahead in registers.  One barrier per chunk.  Epilogue: the two
-// k-phase tiles summed through LDS (q0 + q1), then, with S > 1, the tagged-slab K-split
-// combine of k_mfma_ks (ks_slab_wait; sums in K-range order: deterministic).  K must be a
-// multiple of 256 (whole chunks; the upload checks).
-// ---------------------------------------------------------------------------
-template <int CT>
-__global__ __launch_bounds__(64 * kNmWaves) void k_nm_mfma4(const unsigned char *__restrict__ A,
-                                                            const f16 *__restrict__ B, f16 *__restrict__ C,
-                                                            uint32_t K, uint32_t S64, uint32_t rows, uint32_t row_base,
-                                                            uint32_t S, uint32_t ncs, uint32_t nwg,
-                                                            float *__restrict__ slabs, uint32_t *__restrict__ arrivals,
-                                                            uint32_t flags) {
-    constexpr uint32_t N = 16 * CT, RB = 32 * CT, UB = 2 * CT;
-    constexpr uint32_t HR = kNmKC / 2;                       // B rows of a half chunk (two k-steps)
-    constexpr uint32_t szH = HR * RB;                         // one ring slot
-    constexpr uint32_t NBW = szH / 16u / (64u * kNmWaves);    // LDS-DMA wave-instructions per wave per half
-    static_assert(CT == 8 || CT == 4, "k_nm_mfma4: 64- or 128-column tiles");
-    static_assert(4 * szH <= 160u * 1024u, "four ring slots");
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t rh = wv >> 1, q = wv & 1u;
-    const uint32_t u = xcd_block(blockIdx.x, nwg);
-    const uint32_t g = u / S, qs = u - g * S;
-    const uint32_t rg = g * 4u + rh;
-    const uint32_t nch = S64 / 4u, c0 = qs * ncs, nc = min(ncs, nch - c0);  // this range's chunks
-    const uint32_t nh = 2u * nc;                                             // ... and half chunks
-    const unsigned char *arow = A + (size_t)rg * S64 * kNmBlockBytes;
-
-    // ---- B half chunk h (k-steps 2h, 2h+1 of the range) -> ring slot h & 3 by LDS-DMA:
-    // wave-instruction i of wave wv fills the 1 KB at unit (wv*NBW + i)*64 (lane-linear), rows
-    // k = (wv*NBW + i)*RPI + lane/UB of the half; the piece permutation rides on the source
-    // address.  b_piece's swizzle of row k depends on i only through bit 3 of k (bit 1 of i at
-    // RPI = 4 rows per instruction, CT = 8; bit 0 at RPI = 8, CT = 4): two per-lane offsets
-    static_assert(64 % UB == 0, "whole B rows per wave-instruction");
-    constexpr uint32_t RPI = 64u / UB;
-    auto par_of = [](uint32_t i) -> uint32_t { return RPI == 4 ? (i >> 1) & 1u : i & 1u; };
-    auto i0_of = [](uint32_t par) -> uint32_t { return RPI == 4 ? 2u * par : par; };
-    uint32_t boff[2];
-#pragma unroll
-    for (uint32_t par = 0; par < 2; par++) {
-        const uint32_t k = (wv * NBW + i0_of(par)) * RPI + lane / UB, sp = lane % UB;
-        boff[par] = (k * N + (b_piece<CT>(k, sp >> 1) * 2u + (sp & 1u)) * 8u) * 2u;
-    }
-    auto issue_b = [&](uint32_t h) {
-        const unsigned char *src0 = reinterpret_cast<const unsigned char *>(B) + ((size_t)c0 * kNmKC + (size_t)h * HR) * N * 2u;
-        unsigned char *buf = lds + (h & 3u) * szH;
-#pragma unroll
-        for (uint32_t i = 0; i < NBW; i++) {
-            const uint32_t par = par_of(i);
-            const uint32_t u0 = (wv * NBW + i) * 64u;
-            __builtin_amdgcn_global_load_lds((const void *)(src0 + boff[par] + (i - i0_of(par)) * RPI * N * 2u),
-                                             (__attribute__((address_space(3))) void *)(buf + u0 * 16u), 16, 0, 0);
-        }
-    };
-    // ---- A block of half h for this wave: k-step 2h + q of the range (positions + four tiles)
-    u32x4 av[3][4];
-    uint2 ai[3];
-#define GS_NM4_ALOAD(h, V, I)                                                                       \
-    {                                                                                             \
-        const unsigned char *blk_ = arow + (size_t)(4u * c0 + 2u * (h) + q) * kNmBlockBytes;     \
-        const u32x2 i_ = ld_once(reinterpret_cast<const u32x2 *>(blk_ + lane * 8u));              \
-        I = make_uint2(i_[0], i_[1]);                                                             \
-        _Pragma("unroll") for (int rt = 0; rt < 4; rt++) V[rt] =                                  \
-            ld_once(reinterpret_cast<const u32x4 *>(blk_ + 512u + rt * 1024u + lane * 16u));      \
-    }
-    constexpr int NAL = 5;  // vector loads of one A block
-    f4v acc[4][CT];
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[rt][ct] = f4v{0.f, 0.f, 0.f, 0.f};
-    // transposed B reads: row k = 64*q + klane + {0, 4, 32, 36} keeps klane's swizzle bits
-    // (k & 3 and bit 3: klane & 7 <= 3, so +4 carries nowhere), so piece ct of row k sits at
-    // fb[h] ^ (ct << 5) + 64*q*RB, fb[h] = the row's byte offset + its swizzled piece 0
-    const uint32_t klane = 8u * (lane >> 4) + ((lane & 15u) >> 2);
-    uint32_t fb[4];
-#pragma unroll
-    for (int hh = 0; hh < 4; hh++) {
-        const uint32_t k = klane + 32u * (hh >> 1) + 4u * (hh & 1);
-        fb[hh] = 64u * q * RB + k * RB + b_piece<CT>(k, 0) * 32u + (lane & 3u) * 8u;
-    }
-#define GS_NM4_BFRAG(lb_, ct, BF)                                                                   \
-    {                                                                                             \
-        s4v t_[4];                                                                                \
-        _Pragma("unroll") for (int hh = 0; hh < 4; hh++)                                          \
-            t_[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v *)(lb_ + (fb[hh] ^ ((uint32_t)(ct) << 5)))); \
-        __builtin_memcpy(&BF, t_, 32);                                                            \
-    }
-#define GS_NM4_COMPUTE(h, V, I)                                                                     \
-    {                                                                                             \
-        const unsigned char *lb_ = lds + ((uint32_t)(h) & 3u) * szH;                              \
-        h8v av_[4];                                                                               \
-        _Pragma("unroll") for (int rt = 0; rt < 4; rt++) __builtin_memcpy(&av_[rt], &V[rt], 16);  \
-        const int ix0_ = (int)I.x, ix1_ = (int)I.y;                                               \
-        h16v bf_[2];                                                                              \
-        GS_NM4_BFRAG(lb_, 0, bf_[0]);                                                             \
-        _Pragma("unroll") for (int ct = 0; ct < CT; ct++) {                                       \
-            if (ct + 1 < CT) GS_NM4_BFRAG(lb_, ct + 1, bf_[(ct + 1) & 1]);                        \
-            const h16v b_ = bf_[ct & 1];                                                          \
-            acc[0][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av_[0], b_, acc[0][ct], ix0_, 0, 0); \
-            acc[1][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av_[1], b_, acc[1][ct], ix0_, 0, 1); \
-            acc[2][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av_[2], b_, acc[2][ct], ix1_, 0, 0); \
-            acc[3][ct] = __builtin_amdgcn_smfmac_f32_16x16x64_f16(av_[3], b_, acc[3][ct], ix1_, 0, 1); \
-        }                                                                                         \
-    }
-    // prologue: B halves 0, 1 and A blocks 0, 1, 2 in flight; half 0 retired (B(1), A(1), A(2)
-    // left in flight: NBW + 2 * NAL loads)
-    issue_b(0u);
-    GS_NM4_ALOAD(0u, av[0], ai[0]);
-    issue_b(1u);  // nh >= 2 (a range holds whole chunks)
-    GS_NM4_ALOAD(1u, av[1], ai[1]);
-    if (nh > 2u) {
-        GS_NM4_ALOAD(2u, av[2], ai[2]);
-        __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(NBW + 2 * NAL) : "memory");
-    } else {
-        __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(NBW + NAL) : "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    // half iteration h: B(h+2) -> slot (h+2)&3 (read last in h-2, two barriers ago), compute h,
-    // A(h+3) into h's register set, retire B(h+1) and A(h+1) (B(h+2), A(h+2), A(h+3) left in
-    // flight), barrier.  B is issued two half iterations ahead, A three.
-#define GS_NM4_ITER(h, SET)                                                                         \
-    {                                                                                             \
-        const bool b2_ = (h) + 2u < nh, a3_ = (h) + 3u < nh;                                      \
-        if (b2_) issue_b((h) + 2u);                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        GS_NM4_COMPUTE(h, av[SET], ai[SET]);                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        if (a3_) GS_NM4_ALOAD((h) + 3u, av[SET], ai[SET]);                                        \
-        /* younger than B(h+1) and A(h+1): A(h+2) (if any), B(h+2), A(h+3) */                      \
-        if (a3_) __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(NBW + 2 * NAL) : "memory");         \
-        else if (b2_) __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(NBW + NAL) : "memory");        \
-        else __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");                                 \
-        __builtin_amdgcn_s_barrier();                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-    }
-    uint32_t h = 0;
-    for (; h + 2u < nh; h += 3u) {
-        GS_NM4_ITER(h, 0);
-        GS_NM4_ITER(h + 1u, 1);
-        GS_NM4_ITER(h + 2u, 2);
-    }
-    if (h < nh) GS_NM4_ITER(h, 0);
-    if (h + 1u < nh) GS_NM4_ITER(h + 1u, 1);
-#undef GS_NM4_ITER
-#undef GS_NM4_COMPUTE
-#undef GS_NM4_BFRAG
-#undef GS_NM4_ALOAD
-    // ---- K-split ticket (wave 0), then the two k-phase tiles summed in LDS: q1 -> q0
-    uint32_t *arr = arrivals + g;
-    uint32_t ticket = 0;
-    if (S > 1 && wv == 0 && lane == 0) ticket = __hip_atomic_fetch_add(arr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    f4v *red = reinterpret_cast<f4v *>(lds);
-    constexpr uint32_t TW = 4 * CT * 64;  // f4v per wave tile
-    uint32_t *flag = reinterpret_cast<uint32_t *>(lds + 4u * TW * 16u);  // (nm4_lds_bytes: after the tiles)
-    if (q == 1u) {
-#pragma unroll
-        for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) red[rh * TW + (rt * CT + ct) * 64u + lane] = acc[rt][ct];
-    }
-    if (S > 1 && wv == 0 && lane == 0) *flag = ticket;
-    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __asm__ volatile("" ::: "memory");
-    if (q == 1u) return;
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[rt][ct] += red[rh * TW + (rt * CT + ct) * 64u + lane];
-    auto store_c = [&](int rt, int ct, const f4v &v) {
-#pragma unroll
-        for (uint32_t i = 0; i < 4; i++) {
-            const uint32_t r = rg * 64u + rt * 16u + 4u * (lane >> 4) + i;
-            if (r < rows) C[(size_t)(row_base + r) * N + ct * 16u + (lane & 15u)] = (f16)v[i];
-        }
-    };
-    if (S == 1) {
-#pragma unroll
-        for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) store_c(rt, ct, acc[rt][ct]);
-        return;
-    }
-    // ---- tagged-slab combine (k_mfma_ks's protocol): slab of unit u = [rh][rt][ct][lane] f4v
-    const uint32_t tk = *flag & 0xffffu, tag = ((*flag >> 16) & 1u) ^ 1u;
-    auto tagged = [&](const f4v &v) {
-        u32x4 w;
-        __builtin_memcpy(&w, &v, 16);
-        w[0] = (w[0] & ~1u) | tag; w[1] = (w[1] & ~1u) | tag; w[2] = (w[2] & ~1u) | tag; w[3] = (w[3] & ~1u) | tag;
-        return w;
-    };
-    f4v *slab = reinterpret_cast<f4v *>(slabs) + (size_t)u * 4u * TW + rh * TW;
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
-            const u32x4 w = tagged(acc[rt][ct]);
-            __asm__ volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(slab + (rt * CT + ct) * 64u + lane), "v"(w) : "memory");
-        }
-    if (tk != S - 1u) return;
-    if (wv == 0 && lane == 0) __hip_atomic_store(arr, tag << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t *err = arrivals + nwg / S;  // the replica's device error word
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
-            f4v sum = {0.f, 0.f, 0.f, 0.f};
-            for (uint32_t qq = 0; qq < S; qq++) {
-                u32x4 w;
-                if (qq == qs) {
-                    w = tagged(acc[rt][ct]);
-                } else {
-                    const f4v *src = reinterpret_cast<const f4v *>(slabs) + (size_t)(g * S + qq) * 4u * TW + rh * TW +
-                                     (rt * CT + ct) * 64u + lane;
-                    w = ks_slab_wait(reinterpret_cast<const uint32_t *>(src), tag, err, GS_KS_FORCE(flags));
-                }
-                w[0] &= ~1u; w[1] &= ~1u; w[2] &= ~1u; w[3] &= ~1u;
-                f4v x;
-                __builtin_memcpy(&x, &w, 16);
-                sum += x;
-            }
-            store_c(rt, ct, sum);
-        }
-}
 // k_permute_rows -- B into a merge-path plan's column order (MP_COL_PERM): row i of Bp is row
 // perm[i] of B (perm: the original column of renumbered column i, most nonzeros first), read
 // by a gather; SCATTER: perm[i] is the new place of column i, B read in order and each row
@@ -4731,159 +2819,4 @@ __global__ __launch_bounds__(256) void k_merge_fixup(const uint32_t *__restrict_
 
 }  // namespace gsk
 
-// ---------------------------------------------------------------------------
-// Host-side helpers shared by the library (kernels/device_plan.hip) and the
-// programs code_generator emits: the kernel-side layouts derived from plan
-// arrays.
-// ---------------------------------------------------------------------------
-#include <string>
-#include <vector>
-
-namespace gsk_host {
-
-// CSR row pointer (u32) of a row-sorted COO row array
-inline std::vector<uint32_t> csr_row_ptr(const std::vector<uint64_t> &row, uint64_t row_num) {
-    std::vector<uint32_t> rp(row_num + 1, 0);
-    for (uint64_t r : row) rp[r + 1]++;
-    for (uint64_t i = 0; i < row_num; i++) rp[i + 1] += rp[i];
-    return rp;
-}
-
-// per fixed-nnz BMT, bit i set iff its i-th nz starts a row (no forced BMW heads)
-inline std::vector<uint64_t> row_start_masks(const std::vector<uint64_t> &row, const std::vector<uint64_t> &first_nz) {
-    std::vector<uint64_t> mask(first_nz.size() - 1, 0);
-    for (size_t i = 0; i + 1 < first_nz.size(); i++) {
-        uint64_t mm = 0;
-        for (uint64_t j = first_nz[i]; j < first_nz[i + 1]; j++)
-            if (j == 0 || row[j] != row[j - 1]) mm |= 1ull << (j - first_nz[i]);
-        mask[i] = mm;
-    }
-    return mask;
-}
-
-// k_row_chunks: BMTs per wave (enough waves to fill 256 CUs eight deep)
-inline uint32_t row_chunk_span(size_t n_bmt) {
-    const size_t u = (n_bmt + 8191) / 8192;
-    return (uint32_t)(u < 8 ? 8 : u);
-}
-
-// rows k_row_chunks leaves to k_finalize_rows: rows without BMTs and rows whose
-// BMTs straddle two waves' ranges (output rows = row_base + plan row)
-inline std::vector<uint32_t> row_chunk_finalize_rows(const std::vector<uint32_t> &bmt_row, uint64_t M, uint32_t U,
-                                                     uint32_t row_base) {
-    std::vector<uint8_t> fin(M, 1);
-    for (uint32_t r : bmt_row) fin[r + row_base] = 0;
-    for (size_t i = U; i < bmt_row.size(); i += U)
-        if (bmt_row[i] == bmt_row[i - 1]) fin[bmt_row[i] + row_base] = 1;
-    std::vector<uint32_t> list;
-    for (uint64_t r = 0; r < M; r++)
-        if (fin[r]) list.push_back((uint32_t)r);
-    return list;
-}
-
-// k_merge_path: nz-exact wave ranges from the plan's merge-path levels, and the
-// compact non-empty rows.  Level w starts at path step p = w*work_size; the
-// reference records (row j's index, p - j) for the first non-empty row j with
-// total_path[j] > p (get_begin_{rows,nzs}_of_level_after_merge_path.cc:84-94).
-// total_path[j] = ends[j] + j, so p == ends[j-1] + j - 1 is the step that
-// closes row j-1: the nonzeros consumed there are ends[j-1] = (p - j) + 1;
-// otherwise p - j.  Consecutive levels are grouped into waves of at least
-// target_steps path steps; waves never have an empty nz range.  snap > 0: a wave
-// boundary strictly inside a row of at most `snap` nonzeros moves to the nearer end of
-// that row, so the row is summed by one wave (no cross-wave combine for it; the
-// reference's own merge path splits such rows over threads and adds them atomically).
-struct merge_path_layout {
-    std::vector<uint32_t> wz, wq, ends, rid, empty;  // empty: output rows without nonzeros
-    // rows split across waves: chain[w] = the wave closing the row open at w's end,
-    // chain[W + w] = the first wave of the row w closes at its head (~0: none)
-    std::vector<uint32_t> chain;
-};
-
-// the split-row chains of a layout (k_merge_path's in-launch combine)
-inline void merge_path_chains(merge_path_layout &L) {
-    const size_t W = L.wz.size() - 1;
-    L.chain.assign(2 * W, 0xffffffffu);
-    uint32_t start = 0xffffffffu;
-    size_t q_last = 0;
-    for (size_t w = 0; w < W; w++) {
-        const uint32_t zlo = L.wz[w], zhi = L.wz[w + 1], q0 = L.wq[w];
-        const bool head_open = zlo > (q0 ? L.ends[q0 - 1] : 0u);
-        q_last = std::max<size_t>(q_last, q0);
-        while (L.ends[q_last] < zhi) q_last++;  // the row holding position zhi - 1
-        const bool end_open = L.ends[q_last] > zhi;
-        const bool through = head_open && end_open && q_last == q0;  // the row spans the whole wave
-        if (head_open && !through) {
-            L.chain[W + w] = start;
-            for (uint32_t v = start; v < w; v++) L.chain[v] = (uint32_t)w;
-            start = 0xffffffffu;
-        }
-        if (end_open && !through) start = (uint32_t)w;
-    }
-}
-
-inline bool merge_path_device_layout(const std::vector<uint64_t> &row, uint64_t row_num,
-                                     const std::vector<uint64_t> &lvl_rows, const std::vector<uint64_t> &lvl_nzs,
-                                     uint64_t work_size, uint32_t row_base, uint64_t target_steps,
-                                     merge_path_layout &out, std::string &why, uint64_t out_rows = 0,
-                                     uint64_t snap = 0) {
-    out = merge_path_layout();
-    std::vector<uint32_t> cnt(row_num, 0);
-    for (uint64_t r : row) {
-        if (r >= row_num) { why = "row index beyond the row count"; return false; }
-        cnt[r]++;
-    }
-    std::vector<uint64_t> crow;  // plan row of compact row j
-    uint64_t acc = 0;
-    for (uint64_t r = 0; r < row_num; r++)
-        if (cnt[r]) {
-            acc += cnt[r];
-            if (acc > 0xffffffffull) { why = "nnz exceeds 32 bits"; return false; }
-            out.ends.push_back((uint32_t)acc);
-            out.rid.push_back((uint32_t)(r + row_base));
-            crow.push_back(r);
-        } else {
-            out.empty.push_back((uint32_t)(r + row_base));
-        }
-    for (uint64_t r = row_base + row_num; r < out_rows; r++) out.empty.push_back((uint32_t)r);
-    const uint64_t R = crow.size();
-    if (R == 0 || lvl_rows.empty() || lvl_nzs.size() != lvl_rows.size() + 1 || lvl_nzs.back() != acc || work_size == 0) {
-        why = "merge-path level arrays do not match the matrix";
-        return false;
-    }
-    uint64_t j = 0, gz = 0, gp = 0;
-    out.wz.push_back(0);
-    out.wq.push_back(0);
-    for (uint64_t w = 0; w < lvl_rows.size(); w++) {
-        while (j < R && crow[j] < lvl_rows[w]) j++;
-        const uint64_t p = w * work_size;
-        if (j == R || crow[j] != lvl_rows[w] || p < j || lvl_nzs[w] != p - j) {
-            why = "merge-path level " + std::to_string(w) + " is not on the path";
-            return false;
-        }
-        uint64_t z = (j >= 1 && p == (uint64_t)out.ends[j - 1] + j - 1) ? (uint64_t)out.ends[j - 1] : p - j;
-        uint64_t q = j;
-        if (w == 0 || p - gp < target_steps) continue;
-        if (snap && q < R) {
-            const uint64_t rs = q ? out.ends[q - 1] : 0, re = out.ends[q];
-            if (z > rs && re - rs <= snap) {
-                if (z - rs <= re - z) {
-                    z = rs;
-                } else {
-                    z = re;
-                    q++;
-                }
-            }
-        }
-        if (z <= gz || z >= acc) continue;
-        out.wz.push_back((uint32_t)z);
-        out.wq.push_back((uint32_t)q);
-        gz = z;
-        gp = p;
-    }
-    out.wz.push_back((uint32_t)acc);
-    out.wq.push_back((uint32_t)R);
-    merge_path_chains(out);
-    return true;
-}
-
-}  // namespace gsk_host
+#include "host_layouts.hpp"

@@ -5,6 +5,7 @@
 #include "index_compress.hpp"
 
 #include <cstdio>
+#include <filesystem>
 #include <fstream>
 #include <sstream>
 #include <sys/stat.h>
@@ -223,7 +224,7 @@ std::string matrix_core_source(const meta_data_set &m, const mc_layout &L, int r
                         : (L.nm_ks ? "k_nm_mfma_ks" : (L.nm4 ? "k_nm_mfma4" : "k_nm_mfma"));
     o << "// kernel_file.hip -- generated by generalsparse_amd code_generator: the matrix-core kernel " << kname << "\n"
       << "// build: sh make_kernel.sh; run: ./a.out [matrix.mtx] [N]  -> perf_result (ms, GFLOP/s)\n"
-      << (L.kind == mc_layout::BM || L.nm_ks || L.rows_flags ? "#define GS_EXPERIMENTS  // an experiments-build kernel\n" : "")
+      << (L.kind == mc_layout::BM || L.nm_ks || L.nm4 || L.rows_flags ? "#define GS_EXPERIMENTS  // an experiments-build kernel\n" : "")
       << "#include \"kernel_lib.hpp\"\n#include <cstdio>\n#include <cstdlib>\n#include <cstring>\n#include <fstream>\n"
       << "#include <string>\n#include <vector>\n\n"
       << "typedef gsk::f16 VT;\n"
@@ -633,20 +634,24 @@ uint64_t code_generator::generate_final_program(int repeat, const std::string &r
         std::ofstream f(dir + "/kernel_file.hip");
         f << (L.kind != mc_layout::NONE ? matrix_core_source(*meta, L, repeat) : generate_gather_source(repeat));
     }
-    // copy the device headers next to the program (code_generator.cc:686-694); they ship
-    // next to the library: <pkg>/csrc/hip_code/{kernel_lib,idx_formula}.hpp
+    // copy the device headers next to the program (the reference's code_generator.cc:686-694);
+    // they ship next to the library: every <pkg>/csrc/hip_code/*.hpp
     std::string hdr_dir;
     Dl_info info;
     if (dladdr((void *)&kernel_family_name, &info) && info.dli_fname) {
         std::string so = info.dli_fname;
         hdr_dir = so.substr(0, so.find_last_of('/') + 1) + "csrc/hip_code/";
     }
-    if (!hdr_dir.empty())
-        for (const char *h : {"kernel_lib.hpp", "idx_formula.hpp", "kernel_consts.hpp"}) {
-            std::ifstream in(hdr_dir + h, std::ios::binary);
-            std::ofstream out(dir + "/" + h, std::ios::binary);
+    if (!hdr_dir.empty()) {
+        std::error_code ec;
+        for (const auto &ent : std::filesystem::directory_iterator(hdr_dir, ec)) {
+            if (ent.path().extension() != ".hpp") continue;
+            std::ifstream in(ent.path(), std::ios::binary);
+            std::ofstream out(dir + "/" + ent.path().filename().string(), std::ios::binary);
             out << in.rdbuf();
         }
+        if (ec) fprintf(stderr, "generalsparse: no device headers copied from %s: %s\n", hdr_dir.c_str(), ec.message().c_str());
+    }
     {
         std::ofstream f(dir + "/make_kernel.sh");
         f << "hipcc --offload-arch=gfx950 -O3 -std=c++17 kernel_file.hip -o a.out\n";

@@ -278,7 +278,7 @@ bool build_mfma_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<ui
 }
 
 // ------------------------------------------------------------------ k_mfma_ks layout
-// Upload layout of k_mfma_ks (kernel_lib.hpp): the K range is split into S ranges of
+// Upload layout of k_mfma_ks (mfma_ks.hpp): the K range is split into S ranges of
 // KR = 32*NS columns; for every (BMTB g, range q, 32-column k-step s) -- unit u = g*S + q --
 // the entries of g's rows in the step's columns, in groups of 8: pos = halfword index in a
 // wave image of 96-B rows (local_row*48 + column - step base), val = f16.  The steps'
@@ -483,7 +483,7 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
 }
 
 // ------------------------------------------------------------------ bitmap records
-// k_mfma_bm (kernel_lib.hpp): see bm_tiles.  Row blocks of up to 96 rows (RT <= 6 mask
+// k_mfma_bm (mfma_bm_exp.hpp): see bm_tiles.  Row blocks of up to 96 rows (RT <= 6 mask
 // bytes per record); K split into S ranges of whole k-steps so nb * S workgroups cover
 // the CUs (s_cfg > 0: that many).
 bool build_bm_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,

@@ -1,7 +1,10 @@
-// ks_launch.hip -- launches of k_mfma_ks (hip_code/kernel_lib.hpp), the K-split,
+// ks_launch.hip -- launches of k_mfma_ks (hip_code/mfma_ks.hpp), the K-split,
 // B-stationary matrix-core kernel for tall BMTB row blocks.  Its own translation unit
 // so the kernel's instantiations build in parallel with device_plan.hip.
-#include "../hip_code/kernel_lib.hpp"
+#include "../hip_code/mfma_ks.hpp"
+#ifdef GS_EXPERIMENTS
+#include "../hip_code/mfma_bm_exp.hpp"
+#endif
 #include "../host/gs_plan.hpp"
 
 #include <cstring>
@@ -418,7 +421,7 @@ void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void 
 }
 
 #ifdef GS_EXPERIMENTS  // diagnostics (s_memtime stamps)
-// diagnostic: k_mfma_bm at N = 32, 65..80-row blocks, 8 waves (stamps: kernel_lib.hpp)
+// diagnostic: k_mfma_bm at N = 32, 65..80-row blocks, 8 waves (stamps: mfma_bm_exp.hpp)
 void debug_bm_timeline(const plan_state &p, const void *B, void *C, uint32_t N, hipStream_t s, uint64_t *host,
                        size_t n_host) {
     const device_plan &d = p.dev;

@@ -278,6 +278,17 @@ def test_generate_program(tmp_path):
     files = set(os.listdir(d))
     assert {"kernel_file.hip", "make_kernel.sh", "kernel_lib.hpp", "THREAD_META_first_nz_indices_0",
             "GLOBAL_META_original_nz_row_indices_0"} <= files
+    # every header reachable from the emitted kernel_lib.hpp was copied along with it
+    todo, seen = ["kernel_lib.hpp"], set()
+    while todo:
+        h = todo.pop()
+        if h in seen:
+            continue
+        seen.add(h)
+        assert h in files, h
+        with open(os.path.join(d, h)) as f:
+            todo += re.findall(r'^\s*#\s*include\s+"([^"]+\.hpp)"', f.read(), re.M)
+    assert len(seen) > 1, seen
     fn = np.loadtxt(os.path.join(d, "THREAD_META_first_nz_indices_0"), dtype=np.uint64)
     np.testing.assert_array_equal(fn, p.array("THREAD_META_first_nz_indices_0"))
 
