@@ -10,7 +10,7 @@ libgeneralsparse.so (include/generalsparse.h):
                       1, 0, 0, 0, 0, 1, 4)
     plan.add_operator("thread_total_reduce_operator", 0, 4, 1)
     plan.compile()                                  # code_generator::compile
-    plan.upload(dtype="f16")
+    plan.upload(dtype="f16")                        # or "f32" / "bf16" (A's values, B and C)
     C = plan.spmm(B)                                # the generated kernel, on the GPU
 
 or the canned token_test pipelines: plan.run_pipeline("warp_segment", N=32).
@@ -20,9 +20,10 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import GS_F16, GS_F32, GsError
+from ._lib import GS_BF16, GS_F16, GS_F32, GsError
 
-__all__ = ["Plan", "Batch", "Rotation", "set_config", "GsError", "GS_F16", "GS_F32", "PIPELINES", "load_library"]
+__all__ = ["Plan", "Batch", "Rotation", "set_config", "GsError", "GS_F16", "GS_F32", "GS_BF16", "PIPELINES", "load_library",
+           "convert_values"]
 
 # token_test.cc pipelines (+ the two compositions this engine adds)
 PIPELINES = ("thread_total", "warp_total", "block_total", "thread_bit_map", "warp_segment",
@@ -52,15 +53,37 @@ def _dtype_code(dtype):
         return GS_F16
     if dtype in (GS_F32, "f32", "fp32", "float", np.float32):
         return GS_F32
+    if dtype in (GS_BF16, "bf16", "bfloat16"):
+        return GS_BF16
     try:
         import torch
         if dtype == torch.float16:
             return GS_F16
         if dtype == torch.float32:
             return GS_F32
+        if dtype == torch.bfloat16:
+            return GS_BF16
     except ImportError:
         pass
     raise ValueError(f"unsupported dtype {dtype}")
+
+
+def convert_values(values, dtype):
+    """fp32 values in a plan dtype's storage type, as upload() stores A's values
+    (gs_convert_values: round to nearest even): a float32 array for "f32", the 16-bit words as a
+    uint16 array for "f16" / "bf16" (numpy has no bfloat16)"""
+    L = _lib.load()
+    code = _dtype_code(dtype)
+    x = np.ascontiguousarray(values, dtype=np.float32).ravel()
+    out = np.empty(x.size, np.float32 if code == GS_F32 else np.uint16)
+    _lib.check(L.gs_convert_values(x.ctypes.data_as(_lib.f32p), x.size, code, ctypes.c_void_p(out.ctypes.data)))
+    return out
+
+
+def _torch_dtype(code):
+    """the torch dtype of B and C for a plan's dtype code"""
+    import torch
+    return {GS_F32: torch.float32, GS_F16: torch.float16, GS_BF16: torch.bfloat16}[code]
 
 
 def index_compression_of_array(a, type_ori=16, branch_max=5):
@@ -89,8 +112,7 @@ def _check_operands(info, B, C, N=None):
     """B (cols x N) and C (rows x N): contiguous GPU tensors of the plan's dtype on one device.
     The kernels read B and write every row of C at stride N, so a short or strided operand would
     be read or written out of bounds; raw pointers (ints) are the caller's responsibility."""
-    import torch
-    want = torch.float16 if info["dtype"] == GS_F16 else torch.float32
+    want = _torch_dtype(info["dtype"])
     if not (B.is_cuda and B.dim() == 2 and B.is_contiguous()):
         raise ValueError("B must be a contiguous 2-D GPU tensor")
     if B.shape[0] != info["cols"]:

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("GS_LIBRARY") or os.path.join(PKG_DIR, "libgeneralspar
 
 GS_F32 = 0
 GS_F16 = 1
+GS_BF16 = 2
 
 u64p = ctypes.POINTER(ctypes.c_uint64)
 f32p = ctypes.POINTER(ctypes.c_float)
@@ -62,6 +63,7 @@ SIGNATURES = {
     "gs_plan_generate_program": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int],
                                  ctypes.c_int),
     "gs_plan_upload": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "gs_convert_values": ([f32p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "gs_plan_add_replica": ([ctypes.c_void_p], ctypes.c_int),
     "gs_spmm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "gs_spmm_replica": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,

@@ -73,7 +73,7 @@ def shape_candidates(M):
 def candidates_for(M, K, nnz, dtype, two_four=False, powerlaw=False):
     """the candidate list of a matrix: the class by value type and structure (2:4 panels,
     power-law rows, size), plus, for fp16 row blocks, the whole-CU-round k_mfma_rows height"""
-    if dtype == "f16":
+    if dtype in ("f16", "bf16"):  # bf16 searches the f16 class (same bytes; off k_mfma_ks its plans run gather kernels)
         if two_four:
             return list(CANDIDATES["f16_2to4"])
         c = list(CANDIDATES["f16"])
@@ -115,8 +115,8 @@ def autotune(M, K, row, col, val, N, dtype="f16", candidates=None, device=0, rep
     is the median over the rounds (the chip's clock drifts from round to round)."""
     import torch
     from . import GsError
-    tdt = torch.float16 if dtype == "f16" else torch.float32
-    e = 2 if dtype == "f16" else 4
+    tdt = {"f16": torch.float16, "bf16": torch.bfloat16}.get(dtype, torch.float32)
+    e = 2 if dtype in ("f16", "bf16") else 4
     dev = torch.device(f"cuda:{device}")
     if candidates is None:
         candidates = candidates_for(M, K, len(row), dtype, two_four=two_four, powerlaw=powerlaw)

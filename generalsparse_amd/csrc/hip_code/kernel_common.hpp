@@ -16,6 +16,9 @@
 namespace gsk {
 
 typedef _Float16 f16;
+// bfloat16 (GS_BF16 plans): (float)bf16 is a 16-bit shift, (bf16)float one round-to-nearest-even
+// conversion (v_cvt_pk_bf16_f32 on gfx950)
+typedef __bf16 bf16;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -154,6 +157,22 @@ typedef short s4v __attribute__((ext_vector_type(4)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s4v lds_s4v;
 typedef _Float16 h16v __attribute__((ext_vector_type(16)));
+// the bf16 MFMA's operands (v_mfma_f32_16x16x32_bf16): 8 x bf16 per lane, as h8v for fp16
+typedef __bf16 b8v __attribute__((ext_vector_type(8)));
+// a matrix-core element type's operand fragment and its 16x16x32 MFMA into fp32 (k_mfma_ks)
+template <class ET> struct mfma_elem;
+template <> struct mfma_elem<f16> {
+    typedef h8v frag;
+    static __device__ __forceinline__ f4v mfma_16x16x32(const frag &a, const frag &b, const f4v &c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct mfma_elem<bf16> {
+    typedef b8v frag;
+    static __device__ __forceinline__ f4v mfma_16x16x32(const frag &a, const frag &b, const f4v &c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
 // 8 bytes at a 2-byte-aligned address (k_mfma_kb / k_mfma_bm value windows)
 typedef uint32_t u32x2_a2 __attribute__((ext_vector_type(2), aligned(2)));
 

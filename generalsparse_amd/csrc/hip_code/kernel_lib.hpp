@@ -632,7 +632,7 @@ __device__ __forceinline__ void bitmap_segment_body(const uint32_t *__restrict__
                     if (r != run_row) {
                         if (run_row != 0xffffffffu) {
                             if (ws) atomic_add_vals<float, CF>(ws + (size_t)(run_row + row_base) * N + c0, run);
-                            else atomic_add_vals<VT, CF>(C + (size_t)(run_row + row_base) * N + c0, run);
+                            else if constexpr (!std::is_same<VT, bf16>::value) atomic_add_vals<VT, CF>(C + (size_t)(run_row + row_base) * N + c0, run);
                         }
                         run_row = r;
 #pragma unroll
@@ -644,7 +644,7 @@ __device__ __forceinline__ void bitmap_segment_body(const uint32_t *__restrict__
                 }
                 if (run_row != 0xffffffffu) {
                     if (ws) atomic_add_vals<float, CF>(ws + (size_t)(run_row + row_base) * N + c0, run);
-                    else atomic_add_vals<VT, CF>(C + (size_t)(run_row + row_base) * N + c0, run);
+                    else if constexpr (!std::is_same<VT, bf16>::value) atomic_add_vals<VT, CF>(C + (size_t)(run_row + row_base) * N + c0, run);
                 }
             }
             __builtin_amdgcn_wave_barrier();

@@ -58,10 +58,12 @@ __device__ constexpr int vmcnt_imm() {
 // P8 (KS_POS8, device_layout.cc pos8_step): tP holds 8 bytes per group -- byte e = bit e of the
 // group's 8 x 16 segment id in bit 7, the entry's (row % 8) << 4 | column % 16 below; the image
 // halfword of a segment sg's entry is 384 * (sg >> 1) + 16 * (sg & 1) + 48 * (b >> 4) + (b & 15)
-template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, bool P8 = false, int NTL = 0>
+// ET (f16 or bf16, GS_BF16 plans): the element type of A's values, B and C.  The kernel moves
+// 16-bit words whatever they hold; ET selects the MFMA (mfma_elem) and the store conversion only
+template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, bool P8 = false, int NTL = 0, class ET = f16>
 __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_row, const u32x4 *__restrict__ tP,
                                         const u32x4 *__restrict__ tV, const u32x2 *__restrict__ steps,
-                                        const f16 *__restrict__ B, f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
+                                        const ET *__restrict__ B, ET *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
                                         uint32_t NS, uint32_t nwg, uint32_t row_base, float *__restrict__ slabs,
                                         uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps, uint32_t bx,
                                         uint32_t prio) {
@@ -196,7 +198,8 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     auto step = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG], u32x4 (&B_)[CT]) {
         const bool live = i < nsw;  // wave-uniform
         const uint32_t gc = CN_;
-        h8v av[RT], bv[CT];
+        typedef typename mfma_elem<ET>::frag frag;
+        frag av[RT], bv[CT];
         if (live) {
             const uint32_t kr = k0 + (wv + i * W) * 32u;
             // the step's B rows into the stage (rows past K as zeros)
@@ -221,7 +224,7 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
             }
             // fragments (LDS runs a wave's operations in order: the reads see the stores)
 #pragma unroll
-            for (int rt = 0; rt < RT; rt++) av[rt] = *reinterpret_cast<const h8v *>(img + arow[rt]);
+            for (int rt = 0; rt < RT; rt++) av[rt] = *reinterpret_cast<const frag *>(img + arow[rt]);
             const uint32_t kb = 8u * (lane >> 4);
 #pragma unroll
             for (int ct = 0; ct < CT; ct++) {
@@ -251,7 +254,7 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
             for (int rt = 0; rt < RT; rt++)
 #pragma unroll
                 for (int ct = 0; ct < CT; ct++)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[rt], bv[ct], acc[rt][ct], 0, 0, 0);
+                    acc[rt][ct] = mfma_elem<ET>::mfma_16x16x32(av[rt], bv[ct], acc[rt][ct]);
             if (i < 16u) GS_KS_STAMP(3u + i);
         }
     };
@@ -330,7 +333,7 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
         if (col >= nv) return;
 #pragma unroll
         for (uint32_t i = 0; i < 4; i++)
-            if (rb + i < R) C[(size_t)(row_base + r0 + rb + i) * N + col0 + col] = (f16)v[i];
+            if (rb + i < R) C[(size_t)(row_base + r0 + rb + i) * N + col0 + col] = (ET)v[i];
     };
     GS_KS_STAMP(21u);
     if (S == 1) {
@@ -395,19 +398,19 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
 #undef GS_KS_STAMP
 }
 
-template <int CT, int RT, int W, int D, int MAXG, bool STAMPS = false, bool AP = true, bool P8 = false, int NTL = 0>
+template <int CT, int RT, int W, int D, int MAXG, bool STAMPS = false, bool AP = true, bool P8 = false, int NTL = 0, class ET = f16>
 __global__ __launch_bounds__(64 * W) void k_mfma_ks(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
                                                     const u32x4 *__restrict__ tP,  // 8 x u16 position per group
-                                                    const u32x4 *__restrict__ tV,  // 8 x f16 value per group
+                                                    const u32x4 *__restrict__ tV,  // 8 x 16-bit value (ET) per group
                                                     const u32x2 *__restrict__ steps,  // per (unit, k-step): first group, count
-                                                    const f16 *__restrict__ B, f16 *__restrict__ C, uint32_t K,
+                                                    const ET *__restrict__ B, ET *__restrict__ C, uint32_t K,
                                                     uint32_t N, uint32_t S, uint32_t NS, uint32_t nwg,
                                                     uint32_t row_base, float *__restrict__ slabs,
                                                     uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps = nullptr,
                                                     uint32_t prio = 0) {
     // nwg == gridDim.x (an argument: kernarg preload)
-    ks_body<CT, RT, W, D, MAXG, STAMPS, AP, P8, NTL>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nwg, row_base, slabs,
-                                                arrivals, stamps, blockIdx.x, prio);
+    ks_body<CT, RT, W, D, MAXG, STAMPS, AP, P8, NTL, ET>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nwg, row_base, slabs,
+                                                    arrivals, stamps, blockIdx.x, prio);
 }
 
 #ifdef GS_EXPERIMENTS
@@ -472,8 +475,8 @@ struct ks_entry {  // 96 B
     const uint32_t *tbr;
     const u32x4 *tP, *tV;
     const u32x2 *steps;
-    const f16 *B;
-    f16 *C;
+    const void *B;  // the instantiation's element type (k_mfma_ks_group ET)
+    void *C;
     float *slabs;
     uint32_t *arrivals;
     uint32_t K, S, NS, nwg, row_base, pad0, pad1, pad2;
@@ -485,7 +488,7 @@ struct ks_group_args {
     ks_entry e[kKsGroupMax];
 };
 
-template <int CT, int RT, int W, int D, int MAXG, bool P8 = false, bool AP = true, int NTL = 0>
+template <int CT, int RT, int W, int D, int MAXG, bool P8 = false, bool AP = true, int NTL = 0, class ET = f16>
 __global__ __launch_bounds__(64 * W) void k_mfma_ks_group(ks_group_args args) {
     const uint32_t bx = blockIdx.x, n = args.n;
     uint32_t sel = 0;
@@ -495,8 +498,9 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_group(ks_group_args args) {
     sel = __builtin_amdgcn_readfirstlane(sel);
     const ks_entry &e = args.e[sel];  // kernel arguments: scalar loads at a computed offset
     if (bx - args.begin[sel] >= e.nwg) return;  // padding up to the next entry's multiple of 8
-    ks_body<CT, RT, W, D, MAXG, false, AP, P8, NTL>(e.tbr, e.tP, e.tV, e.steps, e.B, e.C, e.K, args.N, e.S, e.NS, e.nwg, e.row_base,
-                                       e.slabs, e.arrivals, nullptr, bx - args.begin[sel], args.pad[0] | (e.pad0 << 8));
+    ks_body<CT, RT, W, D, MAXG, false, AP, P8, NTL, ET>(e.tbr, e.tP, e.tV, e.steps, (const ET *)e.B, (ET *)e.C, e.K, args.N, e.S, e.NS,
+                                                   e.nwg, e.row_base, e.slabs, e.arrivals, nullptr, bx - args.begin[sel],
+                                                   args.pad[0] | (e.pad0 << 8));
 }
 
 }  // namespace gsk

@@ -170,7 +170,7 @@ void spmm_all(gs_plan *p, int replica, const void *B, void *C, uint32_t N, hipSt
     }
     auto ks = kernel_states(p);
     const int dtype = ks.front()->dev.dtype;
-    const size_t e = dtype == 0 ? 4 : 2;
+    const size_t e = gs::elem_bytes(dtype);
     for (auto &g : p->gaps)
         if (g.second > g.first)
             gs::memset_rows(C, g.first, g.second, N, e, stream);
@@ -746,6 +746,13 @@ int gs_plan_upload(gs_plan_t *p, int dtype, int device) {
             }
             if (at < p->st.M) p->gaps.push_back({at, p->st.M});
         }
+    });
+}
+
+int gs_convert_values(const float *in, uint64_t n, int dtype, void *out) {
+    return guard([&] {
+        GS_CHECK(n == 0 || (in && out), "null argument");
+        gs::convert_values(in, n, dtype, out);
     });
 }
 

@@ -29,6 +29,26 @@ uint16_t f32_to_f16_bits(float f) {
     return (uint16_t)h;
 }
 
+// bf16 is fp32's upper half: round the dropped 16 bits to nearest even.  The carry runs
+// into the exponent, so the largest finite values round to Inf and fp32 denormals round by
+// the same rule; a NaN keeps its upper bits with the quiet bit set.
+uint16_t f32_to_bf16_bits(float f) {
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    if ((x & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((x >> 16) | 0x0040u);
+    return (uint16_t)((x + 0x7fffu + ((x >> 16) & 1u)) >> 16);
+}
+
+void convert_values(const float *in, uint64_t n, int dtype, void *out) {
+    GS_CHECK(dtype_ok(dtype), "dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)");
+    if (dtype == kF32) {
+        if (n) std::memcpy(out, in, n * sizeof(float));
+        return;
+    }
+    uint16_t *o = static_cast<uint16_t *>(out);
+    for (uint64_t i = 0; i < n; i++) o[i] = value_bits16(in[i], dtype);
+}
+
 // Rows as the matrix-core layouts need them: each row's columns ascending and
 // distinct.  The reference accepts any column order inside a row and its gather
 // kernels add repeated coordinates, so entries are stably sorted by column and
@@ -294,7 +314,7 @@ bool build_mfma_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<ui
 
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,
-                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why) {
+                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype) {
     const uint64_t nb = tb_rows.size() - 1;
     if (nb == 0 || K == 0) { why = "empty plan"; return false; }
     if (N == 0 || N % 8 != 0) { why = "N must be a multiple of 8"; return false; }
@@ -447,7 +467,7 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
                         pos.push_back((uint16_t)(i * RS + (col[e] - base)));
                         prow.push_back((uint16_t)i);
                         pcol.push_back((uint16_t)(col[e] - base));
-                        hv.push_back(f32_to_f16_bits(vals[e]));
+                        hv.push_back(value_bits16(vals[e], dtype));
                     }
                     cur[i] = e;
                 }
@@ -705,10 +725,15 @@ mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &s
     const config_t cfg = get_config();
     const int64_t Nd = cfg.DENSE_MATRIX_SIZE;
     L.N = (uint32_t)std::max<int64_t>(0, Nd);
-    if (dtype != 1) { L.why = "fp32 plan"; return L; }
+    if (dtype == kF32) { L.why = "fp32 plan"; return L; }
+    GS_CHECK(dtype_ok(dtype), "dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)");
+    // bf16 plans run k_mfma_ks only: the 2:4 panels, k_mfma_rows and the experiments layouts are
+    // fp16 kernels, and a bf16 plan they would have taken runs its gather family
+    const bool bf = dtype == kBF16;
     const uint64_t row_num = row_num_of_sub_matrix(m, sb);
     const auto &rows = m.u(GLOBAL_META, "nz_row_indices", sb);
-    if (sp.family == KF_ROW_CHUNKS && !sp.interleaved && cfg.NM_MFMA && (Nd == 8 || Nd == 16 || Nd == 32 || Nd == 64 || Nd == 128)) {
+    if (bf && sp.family == KF_ROW_CHUNKS) { L.why = "bf16 plan: k_nm_mfma is an fp16 kernel"; return L; }
+    if (sp.family == KF_ROW_CHUNKS &&!sp.interleaved && cfg.NM_MFMA && (Nd == 8 || Nd == 16 || Nd == 32 || Nd == 64 || Nd == 128)) {
         // col-direction BMTs that are 2:4 panels: sparse matrix cores, self-contained blocks
         const auto &col = m.u(GLOBAL_META, "nz_col_indices", sb);
         auto vals = m.get_element(GLOBAL_META, "nz_vals", sb)->meta_data_arr;
@@ -747,14 +772,18 @@ mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &s
     L.tbr = m.u(TBLOCK_META, "first_row_indices", sb);
     const canon_rows cr = canonical_rows(rp0, col, *vals);
     const uint32_t N = (uint32_t)Nd;
-    if (cfg.MFMA_BM && build_bm_tiles(L.tbr, cr.rp, cr.col, cr.val, K, N, cfg.BM_SPLIT, cfg.BM_WAVES,
-                                      cfg.MFMA_MAX_FILL, L.bm, L.why)) {
+    if (!bf && cfg.MFMA_BM && build_bm_tiles(L.tbr, cr.rp, cr.col, cr.val, K, N, cfg.BM_SPLIT, cfg.BM_WAVES,
+                                             cfg.MFMA_MAX_FILL, L.bm, L.why)) {
         L.kind = mc_layout::BM;
         return L;
     }
-    if (cfg.MFMA_KS &&
-        build_ks_tiles(L.tbr, cr.rp, cr.col, cr.val, K, N, cfg.KS_SPLIT, cfg.KS_MIN_ROWS, cfg.MFMA_MAX_FILL, L.ks, L.why)) {
+    if (cfg.MFMA_KS && build_ks_tiles(L.tbr, cr.rp, cr.col, cr.val, K, N, cfg.KS_SPLIT, cfg.KS_MIN_ROWS, cfg.MFMA_MAX_FILL,
+                                      L.ks, L.why, dtype)) {
         L.kind = mc_layout::KS;
+        return L;
+    }
+    if (bf) {
+        L.why = "bf16 plan off k_mfma_ks (" + (cfg.MFMA_KS ? L.why : std::string("MFMA_KS off")) + "): k_mfma_rows is an fp16 kernel";
         return L;
     }
     // k_mfma_rows: its variant from the config, fixed here

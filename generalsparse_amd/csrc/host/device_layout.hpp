@@ -20,6 +20,18 @@ constexpr uint32_t kKsWaves = 8, kKsDepth = 2;
 
 // fp32 -> fp16 bits, round to nearest even (bit-identical to the device conversion)
 uint16_t f32_to_f16_bits(float f);
+// fp32 -> bf16 bits, round to nearest even (NaN stays a quiet NaN, overflow rounds to Inf)
+uint16_t f32_to_bf16_bits(float f);
+
+// the plan dtypes (include/generalsparse.h GS_F32 / GS_F16 / GS_BF16)
+constexpr int kF32 = 0, kF16 = 1, kBF16 = 2;
+inline bool dtype_ok(int dtype) { return dtype == kF32 || dtype == kF16 || dtype == kBF16; }
+// bytes of one element of A's values, B and C
+inline uint32_t elem_bytes(int dtype) { return dtype == kF32 ? 4u : 2u; }
+// the 16-bit storage word of a value at a 16-bit dtype (the upload's conversion; gs_convert_values)
+inline uint16_t value_bits16(float f, int dtype) { return dtype == kBF16 ? f32_to_bf16_bits(f) : f32_to_f16_bits(f); }
+// gs_convert_values: n values into the dtype's storage type (float or 16-bit words)
+void convert_values(const float *in, uint64_t n, int dtype, void *out);
 
 struct canon_rows {
     std::vector<uint32_t> rp;
@@ -83,7 +95,7 @@ inline uint32_t ks_col_tiles_ct(uint32_t N, uint32_t CT) { return (N + 16 * CT -
 
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,
-                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why);
+                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype = kF16);
 
 // k_mfma_bm upload layout: unit u = (BMTB g, K range q) of NS 32-column k-steps; per
 // (u*NS + step)*64 + lane one 8-byte record (rec[2i] = mask bytes of tiles 0..3, rec[2i+1]

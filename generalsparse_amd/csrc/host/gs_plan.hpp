@@ -34,7 +34,7 @@ enum { MP_PART_COL, MP_PART_VAL, MP_PART_WZ, MP_PART_WQ, MP_PART_ENDS, MP_PART_R
 
 struct device_plan {
     int device = 0;
-    int dtype = 1;         // 0 fp32, 1 fp16 (values, B and C)
+    int dtype = 1;         // 0 fp32, 1 fp16, 2 bf16 (values, B and C; device_layout.hpp kF32 / kF16 / kBF16)
     int col_bytes = 2;     // 2 (u16) or 4 (u32)
     int scf = 4;           // sparse entries per vector load
     bool needs_memset = false;

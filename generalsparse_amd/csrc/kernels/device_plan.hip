@@ -374,10 +374,10 @@ static void upload_col_parts(plan_state &p, device_arrays &a, const std::vector<
     }
     a.cperm = dev_copy(d, gather);
     const uint32_t Nd = (uint32_t)std::max<int64_t>(1, get_config().DENSE_MATRIX_SIZE);
-    const size_t bb = (size_t)K * Nd * (d.dtype == 0 ? 4u : 2u);
+    const size_t bb = (size_t)K * Nd * elem_bytes(d.dtype);
     HIP_OK(hipMalloc(&a.bperm, std::max<size_t>(bb, 16)));
     d.allocations.push_back(a.bperm);
-    const uint32_t cfv = d.dtype == 0 ? 4u : 8u, cf = Nd % cfv == 0 ? cfv : 1u;
+    const uint32_t cfv = 16u / elem_bytes(d.dtype), cf = Nd % cfv == 0 ? cfv : 1u;
     const uint32_t X = std::min<uint32_t>(64u, pow2ceil_u((Nd + cf - 1) / cf));
     const uint64_t target = (uint64_t)gsk::kMpItems * (64u / X);
     a.pp.assign((size_t)P * kMpPartPtrs, nullptr);
@@ -495,7 +495,7 @@ void upload_csr(plan_state &p, device_arrays &a) {
         d.perm_scatter = get_config().MP_PERM_SCATTER != 0;
         a.cperm = dev_copy(d, d.perm_scatter ? rank : perm);  // scatter: new place of each column
         // the gathered B: K rows of the plan's dense width (launches check N <= ws_n = that width)
-        const size_t bb = (size_t)p.K * (size_t)std::max<int64_t>(1, get_config().DENSE_MATRIX_SIZE) * (d.dtype == 0 ? 4u : 2u);
+        const size_t bb = (size_t)p.K * (size_t)std::max<int64_t>(1, get_config().DENSE_MATRIX_SIZE) * elem_bytes(d.dtype);
         HIP_OK(hipMalloc(&a.bperm, std::max<size_t>(bb, 16)));
         d.allocations.push_back(a.bperm);
     } else if (d.col_bytes == 2) {
@@ -504,20 +504,21 @@ void upload_csr(plan_state &p, device_arrays &a) {
     } else {
         a.col = dev_copy(d, to_u32(col, "column index"), kPad);
     }
-    if (d.dtype == 0) {
-        std::vector<float> v(nnz);
-        for (uint64_t i = 0; i < nnz; i++) v[i] = (float)vals->read_float_from_arr(i);
+    // the values in the plan's storage type (convert_values: what gs_convert_values returns)
+    std::vector<float> v(nnz);
+    for (uint64_t i = 0; i < nnz; i++) v[i] = (float)vals->read_float_from_arr(i);
+    if (d.dtype == kF32) {
         a.val = dev_copy(d, v, kPad);
     } else {
-        std::vector<uint16_t> v(nnz);
-        for (uint64_t i = 0; i < nnz; i++) v[i] = f32_to_f16_bits((float)vals->read_float_from_arr(i));
-        a.val = dev_copy(d, v, kPad);
+        std::vector<uint16_t> h(nnz);
+        convert_values(v.data(), nnz, d.dtype, h.data());
+        a.val = dev_copy(d, h, kPad);
     }
 }
 
 void upload_plan(plan_state &p, int dtype, int device) {
     GS_CHECK(p.cg && p.cg->is_compiled(), "plan must be compiled before upload");
-    GS_CHECK(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (fp16)");
+    GS_CHECK(dtype_ok(dtype), "dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)");
     free_device(p);
     HIP_OK(hipSetDevice(device));
     const kernel_spec &sp = p.cg->get_kernel_spec();
@@ -587,13 +588,13 @@ void upload_plan(plan_state &p, int dtype, int device) {
     uint64_t maxc = 0;
     for (uint64_t c : col) maxc = std::max(maxc, c);
     d.col_bytes = maxc <= 0xffff ? 2 : 4;
-    const bool defer_csr = dtype == 1 && get_config().MFMA_TILES &&
+    const bool defer_csr = dtype != kF32 && get_config().MFMA_TILES &&
                            (sp.family == KF_WARP_TOTAL || sp.family == KF_BLOCK_TOTAL) &&
                            m.is_exist(TBLOCK_META, "first_row_indices", sb);
     if (sp.family == KF_MERGE_PATH) {
         // MP_COL_PERM (decided before the CSR upload, which renumbers the columns)
         const config_t cfg = get_config();
-        const uint64_t b_bytes = p.K * (uint64_t)std::max<int64_t>(1, cfg.DENSE_MATRIX_SIZE) * (dtype == 0 ? 4u : 2u);
+        const uint64_t b_bytes = p.K * (uint64_t)std::max<int64_t>(1, cfg.DENSE_MATRIX_SIZE) * elem_bytes(dtype);
         d.col_perm = !sp.interleaved && p.K < (1ull << 32) &&
                      (cfg.MP_COL_PERM > 0 || (cfg.MP_COL_PERM < 0 && b_bytes >= (64ull << 20)));
         // MP_COL_PARTS (fp32 plans of the whole matrix, one column tile: N <= 32): the renumbered
@@ -769,7 +770,7 @@ void upload_plan(plan_state &p, int dtype, int device) {
                 for (size_t i = 0; i + 1 < wr.size(); i++) mw = std::max<uint64_t>(mw, wr[i + 1] - wr[i]);
                 lds_worth = mt >= 16 && mw >= 2;
             }
-            if (sp.tblock_parent && get_config().LDS_STAGE_B && lds_worth) {
+            if (sp.tblock_parent && get_config().LDS_STAGE_B && lds_worth && dtype != kBF16) {  // (k_lds_rows*: fp32 / fp16 kernels)
                 lds_tiles t;
                 std::string why;
                 const uint32_t Nd = (uint32_t)get_config().DENSE_MATRIX_SIZE;
@@ -791,7 +792,7 @@ void upload_plan(plan_state &p, int dtype, int device) {
                 const uint32_t want = cfg_ks > 0 ? (uint32_t)cfg_ks
                                                  : (nbt0 * 2 <= wg_aim ? (uint32_t)std::max<uint64_t>(1, wg_aim / std::max<uint64_t>(nbt0, 1)) : 1u);
                 if (build_lds_tiles(m.u(TBLOCK_META, "first_row_indices", sb), m.u(TBLOCK_META, "first_BMW_indices", sb),
-                                    m.u(WARP_META, "first_row_indices", sb), rp, col, p.K, Nd, dtype ? 2u : 4u, budget,
+                                    m.u(WARP_META, "first_row_indices", sb), rp, col, p.K, Nd, elem_bytes(dtype), budget,
                                     t, why, dma, want)) {
                     d.lds = true;
                     d.lds_dma = dma;
@@ -815,7 +816,7 @@ void upload_plan(plan_state &p, int dtype, int device) {
                     } else {
                         std::vector<uint16_t> v(t.src.size());
                         for (size_t i = 0; i < v.size(); i++)
-                            v[i] = t.src[i] == ~0u ? 0 : f32_to_f16_bits((float)vals->read_float_from_arr(t.src[i]));
+                            v[i] = t.src[i] == ~0u ? 0 : value_bits16((float)vals->read_float_from_arr(t.src[i]), dtype);
                         a.tval = dev_copy(d, v, kPad);
                     }
                     d.bytes_tile = d.bytes_A - before;
@@ -860,8 +861,8 @@ void upload_plan(plan_state &p, int dtype, int device) {
             a.a3 = dev_copy(d, to_u32(m.u(THREAD_META, "segment_empty_row_indices", sb), "segment_empty_row_indices"));
             d.n_units = nb;
             d.scf = 4;
-            if (dtype == 1) {
-                // fp16 C: rows whose nonzeros span BMTs accumulate in an fp32 workspace and
+            if (dtype != kF32) {
+                // fp16 / bf16 C: rows whose nonzeros span BMTs accumulate in an fp32 workspace and
                 // are rounded once by k_finalize_rows, which also writes the empty rows (no memset)
                 const uint64_t rb = d.row_base;
                 std::vector<uint32_t> rp = csr_row_ptr(rows, row_num);
@@ -932,7 +933,7 @@ void upload_plan(plan_state &p, int dtype, int device) {
             // wave ranges decoded from the merge-path levels; S = 64/X slots per wave as launched
             const POS_TYPE L = sp.merge_level;
             const uint32_t Nd = (uint32_t)std::max<int64_t>(1, get_config().DENSE_MATRIX_SIZE);
-            const uint32_t cfv = dtype == 0 ? 4u : 8u, cf = Nd % cfv == 0 ? cfv : 1u;
+            const uint32_t cfv = 16u / elem_bytes(dtype), cf = Nd % cfv == 0 ? cfv : 1u;
             const uint32_t X = std::min<uint32_t>(64u, pow2ceil_u((Nd + cf - 1) / cf));
             const uint64_t target = (uint64_t)gsk::kMpItems * (64u / X);  // >= one round per wave
             if (d.mp_parts > 1) {  // the partitions' layouts are built with their CSRs (upload_col_parts)
@@ -983,7 +984,7 @@ void upload_plan(plan_state &p, int dtype, int device) {
     if (sb == 0 && !pidx && prows > p.M) {
         d.pad_rows = prows;
         d.pad_N = (uint32_t)std::max<int64_t>(1, get_config().DENSE_MATRIX_SIZE);
-        a.pad_out = dev_copy(d, std::vector<uint32_t>((prows * d.pad_N * (dtype == 0 ? 4u : 2u) + 3) / 4, 0u));
+        a.pad_out = dev_copy(d, std::vector<uint32_t>((prows * d.pad_N * elem_bytes(dtype) + 3) / 4, 0u));
     }
     d.replicas.push_back(a);
     p.uploaded = true;
@@ -1059,9 +1060,12 @@ void combine_parts(const void *const *parts, const uint32_t *rows, uint32_t n, v
     const uint64_t total = P * N;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
     if (blocks == 0) return;
-    if (dtype == 0)
+    if (dtype == kF32)
         hipLaunchKernelGGL(gsk::k_combine_parts<float>, dim3(blocks), dim3(256), 0, stream,
                            (const float *const *)parts, rows, n, (float *)C + row0 * N, total, N);
+    else if (dtype == kBF16)
+        hipLaunchKernelGGL(gsk::k_combine_parts<gsk::bf16>, dim3(blocks), dim3(256), 0, stream,
+                           (const gsk::bf16 *const *)parts, rows, n, (gsk::bf16 *)C + row0 * N, total, N);
     else
         hipLaunchKernelGGL(gsk::k_combine_parts<gsk::f16>, dim3(blocks), dim3(256), 0, stream,
                            (const gsk::f16 *const *)parts, rows, n, (gsk::f16 *)C + row0 * N, total, N);
@@ -1077,6 +1081,9 @@ void free_device(plan_state &p) {
 }
 
 static void launch_body(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream) {
+    // (the upload builds no other layout for a bf16 plan: choose_matrix_core_layout, LDS_STAGE_B)
+    GS_CHECK(p.dev.dtype != kBF16 || (!p.dev.nm && !p.dev.lds && (!p.dev.mfma || p.dev.ks)),
+             "bf16 plans run k_mfma_ks or a gather family: the other matrix-core and LDS kernels are fp16 / fp32 kernels");
     if (p.dev.nm) {
         launch_nm(p, p.dev.replicas[replica], B, C, N, stream);
         return;
@@ -1106,7 +1113,7 @@ void launch_spmm(plan_state &p, int replica, const void *B, void *C, uint32_t N,
         void *scr = p.dev.replicas[replica].pad_out;
         launch_body(p, replica, B, scr, N, stream);
         HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(C, scr, (size_t)p.M * N * (p.dev.dtype == 0 ? 4u : 2u), hipMemcpyDeviceToDevice, stream));
+        HIP_OK(hipMemcpyAsync(C, scr, (size_t)p.M * N * elem_bytes(p.dev.dtype), hipMemcpyDeviceToDevice, stream));
         return;
     }
     launch_body(p, replica, B, C, N, stream);

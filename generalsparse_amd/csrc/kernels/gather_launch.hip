@@ -121,7 +121,8 @@ void launch_family(const plan_state &p, const device_arrays &a, const VT *B, VT 
             break;
         }
         case KF_WARP_TOTAL: {
-            if constexpr (CF * sizeof(VT) == 16) {
+            // (k_lds_rows: fp32 / fp16 kernels; the upload builds no LDS tiles for a bf16 plan)
+            if constexpr (CF * sizeof(VT) == 16 && !std::is_same<VT, gsk::bf16>::value) {
                 if (d.lds && N == d.lds_N) {
                     launch_lds<VT, CF>(p, a, B, C, N, s);
                     break;
@@ -173,6 +174,11 @@ void launch_family(const plan_state &p, const device_arrays &a, const VT *B, VT 
             size_t lds = (size_t)4 * S * 2 * X * CF * sizeof(float);
             // the fp32 workspace is sized for the plan's dense width; other widths use fp16 atomics
             const bool use_ws = a.ws && N == d.ws_n;
+            // ... but never bf16 ones: each add would round the sum to 8 significant bits
+            if constexpr (std::is_same<VT, gsk::bf16>::value)
+                GS_CHECK(use_ws, "bf16 bitmap-segment plan built for N=" + std::to_string(d.ws_n) +
+                                     ": at another N its rows would be summed by 16-bit atomic adds, which bf16 "
+                                     "plans refuse (re-run the pipeline for this N)");
             if (!use_ws)
                 HIP_OK(hipMemsetAsync(C + (size_t)d.out_lo * N, 0, (size_t)(d.n_out_rows - d.out_lo) * N * sizeof(VT), s));
             hipLaunchKernelGGL((gsk::k_bitmap_segment<VT, CT, CF, SCF>), dim3(std::max(gx, 1u), tiles), dim3(256),
@@ -333,8 +339,12 @@ void dispatch_vt(const plan_state &p, const device_arrays &a, const void *B, voi
 
 
 void launch_gather(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
-    if (p.dev.dtype == 0) dispatch_vt<float, 4>(p, a, B, C, N, s);
-    else dispatch_vt<gsk::f16, 8>(p, a, B, C, N, s);
+    switch (p.dev.dtype) {
+        case kF32: dispatch_vt<float, 4>(p, a, B, C, N, s); break;
+        case kF16: dispatch_vt<gsk::f16, 8>(p, a, B, C, N, s); break;
+        case kBF16: dispatch_vt<gsk::bf16, 8>(p, a, B, C, N, s); break;
+        default: throw gs_error("plan dtype outside fp32 / fp16 / bf16");
+    }
 }
 
 #ifdef GS_EXPERIMENTS

@@ -1,6 +1,9 @@
 // ks_launch.hip -- launches of k_mfma_ks (hip_code/mfma_ks.hpp), the K-split,
 // B-stationary matrix-core kernel for tall BMTB row blocks.  Its own translation unit
 // so the kernel's instantiations build in parallel with device_plan.hip.
+// Built twice (Makefile): ks_launch.o holds the fp16 instantiations and every entry point,
+// ks_launch_bf16.o (-DGS_KS_BF16_OBJECT) only the bf16 twins behind launch_ks_bf16 /
+// launch_ks_group_bf16, so the two sets of kernels compile in parallel.
 #include "../hip_code/mfma_ks.hpp"
 #ifdef GS_EXPERIMENTS
 #include "../hip_code/mfma_bm_exp.hpp"
@@ -42,14 +45,24 @@ void grant_lds(int device, KERN kern, size_t bytes) {
     }
 }
 
-template <int CT, int RT, int MAXG, bool STAMPS = false, int W = (int)kKsWaves>
-void launch_ks_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B, gsk::f16 *C, uint32_t N, hipStream_t s,
+// ET: the plan's 16-bit element type (gsk::f16, or gsk::bf16 for GS_BF16 plans).  The bf16 twins are
+// built for the release instantiations only (8 waves, apart layout, 16-bit positions, KS_NT 0 / 1):
+// the experiments-build variants below stay fp16 kernels and refuse a bf16 plan
+template <int CT, int RT, int MAXG, bool STAMPS = false, int W = (int)kKsWaves, class ET = gsk::f16>
+void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s,
                  uint64_t *stamps = nullptr) {
     const device_plan &d = p.dev;
+    constexpr bool F16 = std::is_same<ET, gsk::f16>::value;
+    if constexpr (!F16) {
+        static_assert(W == (int)kKsWaves && !STAMPS, "bf16: the release instantiations only");
+        GS_CHECK(d.waves == kKsWaves && !d.ks_p8 && d.ks_ap && !d.ks_persist,
+                 "k_mfma_ks at bf16 is built for 8 waves, 16-bit positions and the apart LDS layout: the experiments "
+                 "variants (KS_WAVES, KS_POS8, KS_APART = 0, KS_PERSIST) are fp16 kernels");
+    }
 #ifdef GS_EXPERIMENTS
     // KS_WAVES = 16 (fixed at upload): every instantiation spills (128 VGPRs at 4 waves per
     // SIMD; C2 48-98 us against 14-30 us with 8 waves, profiles/r04a), experiments build only
-    if constexpr (W == (int)kKsWaves && !STAMPS) {
+    if constexpr (F16 && W == (int)kKsWaves && !STAMPS) {
         if (d.waves == 16) {
             launch_ks_k<CT, RT, MAXG, false, 16>(p, a, B, C, N, s, stamps);
             return;
@@ -63,7 +76,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B,
         }
     }
     // GS_KS_DEPTH=1/3/4 (look-ahead sweep against kKsDepth = 2, N = 32 on the C2 / attn / fc1 instantiations)
-    if constexpr (W == (int)kKsWaves && !STAMPS && CT == 2 &&
+    if constexpr (F16 && W == (int)kKsWaves && !STAMPS && CT == 2 &&
                   ((RT == 3 && MAXG == 1) || (RT == 4 && MAXG == 2) || (RT == 5 && MAXG <= 2) || (RT == 7 && MAXG == 3))) {
         static const int dep = getenv("GS_KS_DEPTH") ? atoi(getenv("GS_KS_DEPTH")) : 0;
         if (dep == 1 || dep == 3 || dep == 4) {
@@ -80,7 +93,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B,
     }
     // measured slower than the default form, experiments build only:
     // KS_WAVES = 4 (256-thread workgroups, overlapped LDS), KS_POS8 (8-bit positions), KS_APART = 0
-    if constexpr (W == (int)kKsWaves && !STAMPS) {
+    if constexpr (F16 && W == (int)kKsWaves && !STAMPS) {
         if (d.waves == 4) {
             if constexpr (CT == 2) {
                 GS_CHECK(!d.ks_ap, "k_mfma_ks with 4 waves runs the overlapped LDS layout");
@@ -103,19 +116,19 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B,
     GS_CHECK(d.waves == kKsWaves && !d.ks_p8 && d.ks_ap,
              "k_mfma_ks with 4 or 16 waves, 8-bit positions or the overlapped LDS layout: experiments build");
 #endif
-    auto kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, STAMPS>;
+    auto kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, STAMPS, true, false, 0, ET>;
     if (d.ks_nt) {  // KS_NT: A's groups by non-temporal loads (N = 32 / 128, 8 waves, the apart layout)
         if constexpr ((CT == 2 || CT == 8) && (W == (int)kKsWaves || W == 12) && !STAMPS) {
             GS_CHECK(d.ks_ap && !d.ks_p8, "k_mfma_ks: non-temporal loads are built for the apart layout, 16-bit positions");
             GS_CHECK(d.ks_nt == 1, "k_mfma_ks: KS_NT is built for A's groups (1)");
-            kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, false, 1>;
+            kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, false, 1, ET>;
         } else {
             throw gs_error("k_mfma_ks: non-temporal loads are built for N = 32 and 128-column tiles, 8 waves");
         }
     }
 #ifdef GS_EXPERIMENTS
     if (d.ks_p8) {  // KS_POS8: 8-bit entry positions (N = 32, 8 waves, the apart layout)
-        if constexpr (CT == 2 && W == (int)kKsWaves && !STAMPS) {
+        if constexpr (F16 && CT == 2 && W == (int)kKsWaves && !STAMPS) {
             GS_CHECK(d.ks_ap, "k_mfma_ks: 8-bit positions are built with the apart LDS layout");
             kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, true>;
         } else {
@@ -123,7 +136,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B,
         }
     }
     if (!d.ks_ap) {  // KS_APART = 0: the partial tiles reuse the stage LDS (N = 32, RT <= 5, MAXG <= 2)
-        if constexpr (CT == 2 && RT <= 5 && MAXG <= 2 && W == (int)kKsWaves)
+        if constexpr (F16 && CT == 2 && RT <= 5 && MAXG <= 2 && W == (int)kKsWaves)
             kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, STAMPS, false>;
         else
             throw gs_error("k_mfma_ks: the overlapped-LDS layout is built for N = 32, RT <= 5, MAXG <= 2");
@@ -132,7 +145,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B,
 #ifdef GS_EXPERIMENTS
     // KS_PERSIST (fixed at upload): a persistent grid of d.ks_persist workgroups pulling units
     if (d.ks_persist) {
-        if constexpr (W == (int)kKsWaves && !STAMPS && (CT == 2 || CT == 8)) {
+        if constexpr (F16 && W == (int)kKsWaves && !STAMPS && (CT == 2 || CT == 8)) {
             GS_CHECK(d.ks_ap && !d.ks_p8 && a.t3 && ks_col_tiles_ct(N, CT) == 1, "k_mfma_ks_persist: 8 waves, apart layout, one column tile");
             auto kp = d.ks_nt ? gsk::k_mfma_ks_persist<CT, RT, W, (int)kKsDepth, MAXG, 1>
                               : gsk::k_mfma_ks_persist<CT, RT, W, (int)kKsDepth, MAXG, 0>;
@@ -161,46 +174,46 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B,
     HIP_OK(hipGetLastError());
 }
 
-template <int CT, int RT>
-void launch_ks_rt(const plan_state &p, const device_arrays &a, const gsk::f16 *B, gsk::f16 *C, uint32_t N, hipStream_t s) {
+template <int CT, int RT, class ET>
+void launch_ks_rt(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s) {
     if constexpr (CT == 8) {  // 128-column tiles: only the (RT, MAXG) pairs that do not spill (ks_ct8_fits)
         GS_CHECK(ks_ct8_fits(RT, p.dev.seg_cap), "k_mfma_ks: 128-column tile instantiation not built for this plan");
         if constexpr (RT == 2) {
             switch (p.dev.seg_cap) {
-                case 1: launch_ks_k<CT, RT, 1>(p, a, B, C, N, s); break;
-                case 2: launch_ks_k<CT, RT, 2>(p, a, B, C, N, s); break;
-                default: launch_ks_k<CT, RT, 3>(p, a, B, C, N, s); break;
+                case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
+                case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
+                default: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
             }
         } else {
-            launch_ks_k<CT, RT, 1>(p, a, B, C, N, s);
+            launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s);
         }
     } else {
         switch (p.dev.seg_cap) {  // MAXG: entry groups per lane per k-step
-            case 1: launch_ks_k<CT, RT, 1>(p, a, B, C, N, s); break;
-            case 2: launch_ks_k<CT, RT, 2>(p, a, B, C, N, s); break;
-            case 3: launch_ks_k<CT, RT, 3>(p, a, B, C, N, s); break;
-            default: launch_ks_k<CT, RT, 4>(p, a, B, C, N, s); break;
+            case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
+            case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
+            case 3: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
+            default: launch_ks_k<CT, RT, 4, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
         }
     }
 }
 
-template <int CT>
-void launch_ks_ct(const plan_state &p, const device_arrays &a, const gsk::f16 *B, gsk::f16 *C, uint32_t N, hipStream_t s) {
+template <int CT, class ET>
+void launch_ks_ct(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s) {
     if constexpr (CT == 8) {  // 128 columns per workgroup: row blocks of up to 48 rows (ks_ct_rt)
         switch (p.dev.maxr) {
-            case 2: launch_ks_rt<CT, 2>(p, a, B, C, N, s); return;
-            case 3: launch_ks_rt<CT, 3>(p, a, B, C, N, s); return;
+            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s); return;
+            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s); return;
             default: throw gs_error("k_mfma_ks: 128-column tiles take row blocks of up to 48 rows");
         }
     } else {
         switch (p.dev.maxr) {  // RT: 16-row tiles per row block (the upload builds RT >= 2)
-            case 2: launch_ks_rt<CT, 2>(p, a, B, C, N, s); break;
-            case 3: launch_ks_rt<CT, 3>(p, a, B, C, N, s); break;
-            case 4: launch_ks_rt<CT, 4>(p, a, B, C, N, s); break;
-            case 5: launch_ks_rt<CT, 5>(p, a, B, C, N, s); break;
-            case 6: if constexpr (CT <= 2) { launch_ks_rt<CT, 6>(p, a, B, C, N, s); break; } [[fallthrough]];
-            case 7: if constexpr (CT <= 2) { launch_ks_rt<CT, 7>(p, a, B, C, N, s); break; } [[fallthrough]];
-            case 8: if constexpr (CT <= 2) { launch_ks_rt<CT, 8>(p, a, B, C, N, s); break; } [[fallthrough]];
+            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s); break;
+            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s); break;
+            case 4: launch_ks_rt<CT, 4, ET>(p, a, B, C, N, s); break;
+            case 5: launch_ks_rt<CT, 5, ET>(p, a, B, C, N, s); break;
+            case 6: if constexpr (CT <= 2) { launch_ks_rt<CT, 6, ET>(p, a, B, C, N, s); break; } [[fallthrough]];
+            case 7: if constexpr (CT <= 2) { launch_ks_rt<CT, 7, ET>(p, a, B, C, N, s); break; } [[fallthrough]];
+            case 8: if constexpr (CT <= 2) { launch_ks_rt<CT, 8, ET>(p, a, B, C, N, s); break; } [[fallthrough]];
             default: throw gs_error("k_mfma_ks: row tiles outside 2..8 (6..8 for N <= 32)");
         }
     }
@@ -285,6 +298,7 @@ void launch_bm_ct(const plan_state &p, const device_arrays &a, const gsk::f16 *B
 
 }  // namespace
 
+#ifndef GS_KS_BF16_OBJECT
 #ifdef GS_EXPERIMENTS
 void launch_bm(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
     const gsk::f16 *b = (const gsk::f16 *)B;
@@ -302,27 +316,33 @@ void launch_bm(const plan_state &, const device_arrays &, const void *, void *, 
     throw gs_error("k_mfma_bm is an experiments-build kernel (make -C generalsparse_amd/csrc exp)", -2);
 }
 #endif
+#endif  // !GS_KS_BF16_OBJECT
 
 // ---- grouped launches (gs_spmm_batch): N = 32 (CT = 2), 8 waves, one instantiation per group
 namespace {
-template <int RT, int MAXG, int W = (int)kKsWaves>
+template <int RT, int MAXG, int W = (int)kKsWaves, class ET = gsk::f16>
 void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
     constexpr bool AP = W == (int)kKsWaves;
+    constexpr bool F16 = std::is_same<ET, gsk::f16>::value;
+    if constexpr (!F16)  // (ks_group_key admits bf16 plans of the release layout only)
+        GS_CHECK(it[0].p->dev.waves == kKsWaves && !it[0].p->dev.ks_p8, "k_mfma_ks_group at bf16: 8 waves, 16-bit positions");
 #ifdef GS_EXPERIMENTS
-    if constexpr (W == (int)kKsWaves) {
+    if constexpr (F16 && W == (int)kKsWaves) {
         if (it[0].p->dev.waves == 4) {  // KS_WAVES = 4: 256-thread workgroups, overlapped LDS
             launch_ks_group_k<RT, MAXG, 4>(it, N, s);
             return;
         }
     }
-    auto kern = it[0].p->dev.ks_p8 ? gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, true, AP>
-                                   : gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, AP>;
+    auto kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, AP, 0, ET>;
+    if constexpr (F16) {
+        if (it[0].p->dev.ks_p8) kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, true, AP>;
+    }
 #else
     GS_CHECK(!it[0].p->dev.ks_p8, "k_mfma_ks_group: 8-bit positions are an experiments-build layout");
-    auto kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, AP>;
+    auto kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, AP, 0, ET>;
 #endif
     if constexpr (AP) {
-        if (it[0].p->dev.ks_nt) kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, true, 1>;
+        if (it[0].p->dev.ks_nt) kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, true, 1, ET>;
     }
     GS_CHECK(!it.empty() && it.size() <= (size_t)gsk::kKsGroupMax, "k_mfma_ks_group: 1..32 entries");
     gsk::ks_group_args args;
@@ -340,8 +360,8 @@ void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStre
         e.tP = (const gsk::u32x4 *)a.tcol;
         e.tV = (const gsk::u32x4 *)a.tval;
         e.steps = (const gsk::u32x2 *)a.t1;
-        e.B = (const gsk::f16 *)it[i].B;
-        e.C = (gsk::f16 *)it[i].C;
+        e.B = it[i].B;
+        e.C = it[i].C;
         e.slabs = a.ws;
         e.arrivals = a.t2;
         e.K = (uint32_t)p.K;
@@ -364,27 +384,68 @@ void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStre
     HIP_OK(hipGetLastError());
 }
 
-template <int RT>
+template <int RT, class ET>
 void launch_ks_group_rt(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
     switch (it[0].p->dev.seg_cap) {
-        case 1: launch_ks_group_k<RT, 1>(it, N, s); break;
-        case 2: launch_ks_group_k<RT, 2>(it, N, s); break;
-        case 3: launch_ks_group_k<RT, 3>(it, N, s); break;
-        default: launch_ks_group_k<RT, 4>(it, N, s); break;
+        case 1: launch_ks_group_k<RT, 1, (int)kKsWaves, ET>(it, N, s); break;
+        case 2: launch_ks_group_k<RT, 2, (int)kKsWaves, ET>(it, N, s); break;
+        case 3: launch_ks_group_k<RT, 3, (int)kKsWaves, ET>(it, N, s); break;
+        default: launch_ks_group_k<RT, 4, (int)kKsWaves, ET>(it, N, s); break;
+    }
+}
+template <class ET>
+void launch_ks_group_et(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
+    switch (it[0].p->dev.maxr) {
+        case 2: launch_ks_group_rt<2, ET>(it, N, s); break;
+        case 3: launch_ks_group_rt<3, ET>(it, N, s); break;
+        case 4: launch_ks_group_rt<4, ET>(it, N, s); break;
+        case 5: launch_ks_group_rt<5, ET>(it, N, s); break;
+        case 6: launch_ks_group_rt<6, ET>(it, N, s); break;
+        case 7: launch_ks_group_rt<7, ET>(it, N, s); break;
+        case 8: launch_ks_group_rt<8, ET>(it, N, s); break;
+        default: throw gs_error("k_mfma_ks_group: row tiles outside 2..8");
+    }
+}
+template <class ET>
+void launch_ks_et(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
+    const ET *b = (const ET *)B;
+    ET *c = (ET *)C;
+    switch (p.dev.ks_ctw) {  // 16-column tiles per workgroup; ks_col_tiles_ct(N, CT) workgroups across N
+        case 1: launch_ks_ct<1, ET>(p, a, b, c, N, s); break;
+        case 2: launch_ks_ct<2, ET>(p, a, b, c, N, s); break;
+        case 4: launch_ks_ct<4, ET>(p, a, b, c, N, s); break;
+        case 8: launch_ks_ct<8, ET>(p, a, b, c, N, s); break;
+        default: throw gs_error("k_mfma_ks: bad column tile count");
     }
 }
 }  // namespace
+
+#ifdef GS_KS_BF16_OBJECT
+void launch_ks_bf16(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
+    launch_ks_et<gsk::bf16>(p, a, B, C, N, s);
+}
+void launch_ks_group_bf16(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
+    launch_ks_group_et<gsk::bf16>(it, N, s);
+}
+#else
+// the bf16 twins (ks_launch_bf16.o)
+void launch_ks_bf16(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
+void launch_ks_group_bf16(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s);
 
 uint32_t ks_group_key(const plan_state &p, uint32_t N) {
     const device_plan &d = p.dev;
     const bool w8 = d.waves == kKsWaves && d.ks_ap, w4 = d.waves == 4 && !d.ks_ap;
     if (!p.uploaded || !d.mfma || !d.ks || d.pad_rows || N != 32 || d.lds_N != 32 || !(w8 || w4) || d.ks_persist) return 0;
+    // bf16: the grouped kernel's twins are the release instantiations (as launch_ks_k)
+    if (d.dtype == kBF16 && (d.ks_p8 || !w8)) return 0;
 #ifndef GS_EXPERIMENTS
     // the release build instantiates the grouped kernel for 16-byte u16-position groups on 8
     // waves only: any other layout runs as single launches (which refuse it themselves)
     if (d.ks_p8 || !w8) return 0;
 #endif
-    return (d.ks_nt << 18) | (w4 ? 1u << 17 : 0u) | (d.ks_p8 ? 1u << 16 : 0u) | (d.maxr << 8) | d.seg_cap;  // NT, waves, P8, RT, MAXG
+    // dtype, NT, waves, P8, RT, MAXG: fp16 and bf16 entries never share a launch
+    return (d.dtype == kBF16 ? 1u << 20 : 0u) | (d.ks_nt << 18) | (w4 ? 1u << 17 : 0u) | (d.ks_p8 ? 1u << 16 : 0u) | (d.maxr << 8) |
+           d.seg_cap;
 }
 
 void launch_ks_group(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
@@ -392,32 +453,18 @@ void launch_ks_group(const std::vector<ks_group_item> &it, uint32_t N, hipStream
     const uint32_t key = ks_group_key(*it[0].p, N);
     GS_CHECK(key != 0, "k_mfma_ks_group: not a groupable k_mfma_ks plan");
     for (const auto &x : it) GS_CHECK(ks_group_key(*x.p, N) == key, "k_mfma_ks_group: entries of different instantiations");
-    switch (it[0].p->dev.maxr) {
-        case 2: launch_ks_group_rt<2>(it, N, s); break;
-        case 3: launch_ks_group_rt<3>(it, N, s); break;
-        case 4: launch_ks_group_rt<4>(it, N, s); break;
-        case 5: launch_ks_group_rt<5>(it, N, s); break;
-        case 6: launch_ks_group_rt<6>(it, N, s); break;
-        case 7: launch_ks_group_rt<7>(it, N, s); break;
-        case 8: launch_ks_group_rt<8>(it, N, s); break;
-        default: throw gs_error("k_mfma_ks_group: row tiles outside 2..8");
-    }
+    // (the key carries the dtype: every entry holds the first one's element type)
+    if (it[0].p->dev.dtype == kBF16) launch_ks_group_bf16(it, N, s);
+    else launch_ks_group_et<gsk::f16>(it, N, s);
 }
 
 void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
-    const gsk::f16 *b = (const gsk::f16 *)B;
-    gsk::f16 *c = (gsk::f16 *)C;
     GS_CHECK(N == p.dev.lds_N, "k_mfma_ks runs the plan's dense width");
     GS_CHECK(p.dev.ks_ctw == ks_ct_rt(N, p.dev.maxr) || (p.dev.ks_ctw == 4 && ks_ct_rt(N, p.dev.maxr) == 8 &&
                                                          !ks_ct8_fits(p.dev.maxr, p.dev.seg_cap)),
              "k_mfma_ks: column tiles disagree with the upload");
-    switch (p.dev.ks_ctw) {  // 16-column tiles per workgroup; ks_col_tiles_ct(N, CT) workgroups across N
-        case 1: launch_ks_ct<1>(p, a, b, c, N, s); break;
-        case 2: launch_ks_ct<2>(p, a, b, c, N, s); break;
-        case 4: launch_ks_ct<4>(p, a, b, c, N, s); break;
-        case 8: launch_ks_ct<8>(p, a, b, c, N, s); break;
-        default: throw gs_error("k_mfma_ks: bad column tile count");
-    }
+    if (p.dev.dtype == kBF16) launch_ks_bf16(p, a, B, C, N, s);
+    else launch_ks_et<gsk::f16>(p, a, B, C, N, s);
 }
 
 #ifdef GS_EXPERIMENTS  // diagnostics (s_memtime stamps)
@@ -440,8 +487,8 @@ void debug_bm_timeline(const plan_state &p, const void *B, void *C, uint32_t N, 
 void debug_ks_timeline(const plan_state &p, const void *B, void *C, uint32_t N, hipStream_t s, uint64_t *host,
                        size_t n_host) {
     const device_plan &d = p.dev;
-    GS_CHECK(N == 32 && d.maxr >= 2 && d.maxr <= 5 && d.seg_cap <= 2 && d.waves == kKsWaves,
-             "k_mfma_ks timeline build: N=32, RT 2..5, MAXG <= 2, 8 waves only");
+    GS_CHECK(N == 32 && d.maxr >= 2 && d.maxr <= 5 && d.seg_cap <= 2 && d.waves == kKsWaves && d.dtype == kF16,
+             "k_mfma_ks timeline build: fp16, N=32, RT 2..5, MAXG <= 2, 8 waves only");
     const size_t n = (size_t)d.n_rows_aux * d.ksplit * ks_col_tiles(N) * kKsWaves * 32;
     uint64_t *dst = nullptr;
     HIP_OK(hipMalloc(&dst, n * 8));
@@ -469,5 +516,7 @@ void debug_ks_timeline(const plan_state &, const void *, void *, uint32_t, hipSt
     throw gs_error("timeline builds are diagnostics of the experiments build (make -C generalsparse_amd/csrc exp)", -2);
 }
 #endif  // GS_EXPERIMENTS
+
+#endif  // !GS_KS_BF16_OBJECT
 
 }  // namespace gs

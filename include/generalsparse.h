@@ -37,11 +37,14 @@ typedef void *gs_stream_t; /* hipStream_t; NULL = default stream */
 
 enum { GS_OK = 0, GS_ERR = -1, GS_ERR_ARG = -2, GS_ERR_HIP = -3,
        GS_ERR_DEVICE = -4 /* a kernel reported a fault in its device error word (gs_plan_device_status) */ };
-enum { GS_F32 = 0, GS_F16 = 1 };
+/* value types of a plan on the device (A's values, B and C alike).  GS_BF16 runs the K-split
+ * matrix-core kernel (k_mfma_ks) and every gather family; plans that would take another
+ * matrix-core or LDS kernel at fp16 run their gather family at bf16. */
+enum { GS_F32 = 0, GS_F16 = 1, GS_BF16 = 2 };
 
 typedef struct {
     const char *pipeline;   /* token_test pipeline name, see gs_plan_run_pipeline */
-    int dtype;              /* GS_F32 / GS_F16 (A values, B and C) */
+    int dtype;              /* GS_F32 / GS_F16 / GS_BF16 (A values, B and C) */
     int dense_n;            /* DENSE_MATRIX_SIZE used to size the plan (token_test argv[2]) */
     int p0, p1;             /* pipeline parameters (sparse_coarsen_factor / rows per BMTB / ...) */
     int ones_values;        /* 1: reference reader semantics, every value := 1 (struct.cc:186-200) */
@@ -54,7 +57,7 @@ typedef struct {
     uint64_t n_units;             /* BMTs / BMWs / BMTBs the kernel walks */
     uint64_t device_bytes_A;      /* HBM bytes of A (metadata + cols + vals) per replica */
     int family;                   /* 1 thread_total, 2 warp_rows, 3 block_rows, 4 bitmap_segment */
-    int col_bytes, dtype, replicas, needs_memset;
+    int col_bytes, dtype /* GS_F32 / GS_F16 / GS_BF16, as uploaded */, replicas, needs_memset;
     char kernel_name[64];
     /* row-block kernels built at upload for dense width lds_n: 1 = LDS-stationary B
      * (k_lds_rows, config LDS_STAGE_B), 2 = matrix cores (k_mfma_rows, MFMA_TILES),
@@ -109,10 +112,18 @@ int gs_plan_sub_matrices(gs_plan_t *p, int *ids, int cap);
 int gs_plan_compile(gs_plan_t *p);
 int gs_plan_generate_program(gs_plan_t *p, const char *root_dir, int repeat, char *dir_out, int dir_out_len);
 
+/* dtype: GS_F32, GS_F16 or GS_BF16 (anything else: GS_ERR).  A's fp32 values are converted
+ * with gs_convert_values; B and C of every later gs_spmm hold the same type. */
 int gs_plan_upload(gs_plan_t *p, int dtype, int device);
+/* the conversion gs_plan_upload applies to A's values: n elements of the dtype's storage type
+ * into `out` (float for GS_F32, 16-bit words for GS_F16 / GS_BF16), round to nearest even;
+ * NaN stays a quiet NaN, +-Inf stay, values past the largest finite value round to +-Inf.
+ * Host only (no device is touched). */
+int gs_convert_values(const float *in, uint64_t n, int dtype, void *out);
 int gs_plan_add_replica(gs_plan_t *p);
 /* C = A * B.  B: K x N row-major, C: M x N row-major, device pointers of the
- * plan's dtype.  Enqueued on `stream`; returns without synchronising.  The library cannot
+ * plan's dtype (float, fp16 or bf16 elements: GS_F32 / GS_F16 / GS_BF16; every kernel
+ * accumulates in fp32 and rounds once, to nearest even, at the store).  Enqueued on `stream`; returns without synchronising.  The library cannot
  * see the extents behind raw pointers: the caller guarantees K x N readable and M x N
  * writable elements (the Python Plan.spmm / Rotation / Batch check their tensors). */
 int gs_spmm(gs_plan_t *p, const void *B, void *C, int N, gs_stream_t stream);
