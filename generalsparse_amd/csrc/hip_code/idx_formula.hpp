@@ -13,6 +13,9 @@
 #pragma once
 
 #include <stdint.h>
+#if defined(__HIP__) || defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // __forceinline__
+#endif
 
 namespace gsk {
 

@@ -1,5 +1,6 @@
-// hip_code/kernel_consts.hpp -- compile-time shapes of the gfx950 kernels in
-// kernel_lib.hpp that the host-side layout builders (host/device_layout.cc) size
+// hip_code/kernel_consts.hpp -- compile-time shapes of the gfx950 kernels in the
+// family headers (mfma_rows.hpp, mfma_ks.hpp, nm_mfma.hpp, merge_path.hpp, ...) that the
+// host-side layout builders (host/device_layout.cc, kernels/device_plan.hip) size
 // their tiles by.  Plain C++ (no device code): included by both sides.
 #pragma once
 
@@ -116,5 +117,8 @@ GSK_HD constexpr size_t nm4_lds_bytes(uint32_t CT) {
     const size_t bufs = (size_t)2 * kNmKC * 32u * CT, red = (size_t)4 * 4 * CT * 64 * 16 + 16;
     return bufs > red ? bufs : red;
 }
+
+// k_merge_path: nonzeros per slot per round
+constexpr uint32_t kMpItems = 8;
 
 }  // namespace gsk

@@ -1,0 +1,54 @@
+// hip_code/parts.hpp -- the element-wise companions of the other families: k_combine_parts
+// (parent-indexed sub-matrices), k_add_parts (MP_COL_PARTS) and k_finalize_rows (fp32 workspace
+// rows).  Instantiated by kernels/device_plan.hip and kernels/gather_launch.hip.
+#pragma once
+
+#include "kernel_common.hpp"
+
+namespace gsk {
+
+// ---------------------------------------------------------------------------
+// rows listed (shared between BMTs, or empty): C = fp16(workspace), workspace
+// re-zeroed for the next launch (companion of k_bitmap_segment with ws and of
+// k_row_chunks)
+// parent-indexed sub-matrices (row_nz_matrix_div_operator): C row r of the divided range is
+// the sum, in sub-matrix order, of row r of every scratch output that has a row r
+template <class VT>
+__global__ __launch_bounds__(256) void k_combine_parts(const VT *const *__restrict__ parts,
+                                                       const uint32_t *__restrict__ rows, uint32_t n,
+                                                       VT *__restrict__ C, uint64_t total, uint32_t N) {
+    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256) {
+        const uint64_t r = e / N;
+        float s = 0.f;
+        for (uint32_t q = 0; q < n; q++)
+            if (r < rows[q]) s += (float)parts[q][e];
+        C[e] = (VT)s;
+    }
+}
+
+// MP_COL_PARTS: C += the fp32 outputs of column partitions 1..n-1, added in partition order
+// (deterministic), C rounded once
+struct mp_part_outs {
+    const float *p[8];
+};
+template <class VT>
+__global__ __launch_bounds__(256) void k_add_parts(VT *__restrict__ C, mp_part_outs parts, uint32_t n, uint64_t total) {
+    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256) {
+        float s = (float)C[e];
+        for (uint32_t q = 0; q < n; q++) s += parts.p[q][e];
+        C[e] = (VT)s;
+    }
+}
+
+template <class VT>
+__global__ __launch_bounds__(256) void k_finalize_rows(const uint32_t *__restrict__ rows, uint32_t n_rows,
+                                                       float *__restrict__ ws, VT *__restrict__ C, uint32_t N) {
+    const size_t total = (size_t)n_rows * N;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t idx = (size_t)rows[e / N] * N + e % N;
+        C[idx] = (VT)ws[idx];
+        ws[idx] = 0.f;
+    }
+}
+
+}  // namespace gsk

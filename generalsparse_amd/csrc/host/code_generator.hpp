@@ -6,7 +6,8 @@
 // (descriptors) to the levels exactly as before (set_reduction_token /
 // open_spec_level_of_paral / set_thread_grid), and compile() lowers that
 // token set onto one of the hand-written gfx950 kernel families in
-// hip_code/kernel_lib.hpp, producing a kernel_spec.  generate_final_program()
+// hip_code/ (one header per family; kernel_lib.hpp is the umbrella the emitted
+// programs include), producing a kernel_spec.  generate_final_program()
 // emits a standalone HIP program (kernel_file.hip + plan files +
 // make_kernel.sh) that instantiates the same family, with the reference's
 // perf_result contract (code_generator.cc:643-648).
@@ -40,7 +41,7 @@ struct reduction_token {
     int size = 0;  // VECTOR_WIDTH / bitmap group size
 };
 
-// gfx950 kernel families (hip_code/kernel_lib.hpp)
+// gfx950 kernel families (hip_code/: the list in kernel_lib.hpp names each family's header)
 enum kernel_family : int {
     KF_NONE = 0,
     KF_THREAD_TOTAL = 1,    // lane group per BMT row (row-sorted, col-padded)

@@ -91,7 +91,7 @@ canon_rows canonical_rows(const std::vector<uint32_t> &rp, const std::vector<uin
 }
 
 // ------------------------------------------------------------------ MFMA tiles
-// Upload layout of k_mfma_rows (kernel_lib.hpp): for BMTB g and column chunk j,
+// Upload layout of k_mfma_rows (mfma_rows.hpp): for BMTB g and column chunk j,
 // the entries of g's rows with columns in [j*KC, (j+1)*KC), in groups of 8:
 // pos[] = 8 x u16 halfword index in the dense image (local_row*(KC+16) +
 // local_col), val[] = 8 x f16; the last group is padded with (row R, value 0),
@@ -607,7 +607,7 @@ bool build_bm_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
 }
 
 // ------------------------------------------------------------------ 2:4 panels
-// Block layout of k_nm_mfma (kernel_lib.hpp) from the plan's COO: every row is
+// Block layout of k_nm_mfma (nm_mfma.hpp) from the plan's COO: every row is
 // cut into 64-column k-steps (the col-direction BMTs of a 2:4 row: 32 entries
 // each), every aligned group of four columns keeps its (at most two) entries as
 // two values + two 2-bit positions.  Duplicate coordinates (col padding of the

@@ -41,7 +41,7 @@ struct canon_rows {
 
 canon_rows canonical_rows(const std::vector<uint32_t> &rp, const std::vector<uint64_t> &col, const universal_array &vals);
 
-// k_mfma_rows upload layout (kernel_lib.hpp): per (BMTB g, 2^lgKC-column chunk j), the
+// k_mfma_rows upload layout (mfma_rows.hpp): per (BMTB g, 2^lgKC-column chunk j), the
 // chunk's entries in groups of 8 = [8 x u16 halfword position in the dense image] +
 // [8 x f16]; seg_start[g*nc + j] the first group
 struct mfma_tiles {

@@ -1,6 +1,8 @@
 // device_plan.hip -- uploads a compiled plan to HBM in the layout of its
-// kernel family and dispatches the gfx950 kernels of hip_code/kernel_lib.hpp.
-#include "../hip_code/kernel_lib.hpp"
+// kernel family and dispatches the gfx950 kernels of hip_code/ through the launch files
+// (gather_launch.hip, mfma_launch.hip, ks_launch.hip); k_combine_parts is launched here.
+#include "../hip_code/parts.hpp"
+#include "../hip_code/host_layouts.hpp"
 #include "../host/gs_plan.hpp"
 #include "../host/index_compress.hpp"
 #include "../host/device_layout.hpp"
@@ -95,7 +97,7 @@ uint32_t pow2ceil_u(uint32_t x) {
 }
 
 // ------------------------------------------------------------------ LDS tiles
-// Chunk-major A layout for k_lds_rows (kernel_lib.hpp): for BMTB g and column
+// Chunk-major A layout for k_lds_rows (lds_rows.hpp): for BMTB g and column
 // chunk j = [j*KC, (j+1)*KC), the entries of g's rows whose columns fall in the
 // chunk, row after row, each row padded to 4 entries (column 0, value 0) and
 // the segment padded to 8 entries so it stages as whole 16-B units.

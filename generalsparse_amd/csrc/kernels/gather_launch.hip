@@ -1,7 +1,11 @@
 // gather_launch.hip -- launches of the CUDA-core gather families (k_thread_total,
 // k_warp_rows, k_block_rows, k_bitmap_segment, k_row_chunks, k_merge_path) and the
-// LDS-staged k_lds_rows (hip_code/kernel_lib.hpp).
-#include "../hip_code/kernel_lib.hpp"
+// LDS-staged k_lds_rows (hip_code/gather.hpp, merge_path.hpp, lds_rows.hpp), with their
+// element-wise companions (parts.hpp).
+#include "../hip_code/gather.hpp"
+#include "../hip_code/parts.hpp"
+#include "../hip_code/lds_rows.hpp"
+#include "../hip_code/merge_path.hpp"
 #include "../host/gs_plan.hpp"
 
 #include <algorithm>
@@ -348,7 +352,7 @@ void launch_gather(const plan_state &p, const device_arrays &a, const void *B, v
 }
 
 #ifdef GS_EXPERIMENTS
-// diagnostic: one merge-path launch with s_memtime stamps per path wave (kernel_lib.hpp)
+// diagnostic: one merge-path launch with s_memtime stamps per path wave (merge_path.hpp)
 void debug_mp_timeline(const plan_state &p, const void *B, void *C, uint32_t N, hipStream_t s, uint64_t *host,
                        size_t n_host) {
     const size_t n = (size_t)p.dev.n_units * 16;

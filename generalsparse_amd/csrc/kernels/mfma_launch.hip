@@ -1,7 +1,11 @@
 // mfma_launch.hip -- launches of the dense-tile matrix-core kernels k_mfma_rows and
-// k_nm_mfma (hip_code/kernel_lib.hpp); k_mfma_ks has ks_launch.hip.  Separate
+// k_nm_mfma (hip_code/mfma_rows.hpp, nm_mfma.hpp); k_mfma_ks has ks_launch.hip.  Separate
 // translation units so the kernel instantiations build in parallel.
-#include "../hip_code/kernel_lib.hpp"
+#include "../hip_code/mfma_rows.hpp"
+#include "../hip_code/nm_mfma.hpp"
+#ifdef GS_EXPERIMENTS
+#include "../hip_code/nm_mfma_exp.hpp"
+#endif
 #include "../host/gs_plan.hpp"
 
 #include <cstdlib>
@@ -39,7 +43,7 @@ void launch_mfma_k(const plan_state &p, const device_arrays &a, const gsk::f16 *
         if (gl == 2 && wct == 6 && nbg == 5) kern = gsk::k_mfma_rows<CT, RT, LGKC, MAXA, false, 2, 5>;
     }
 #ifdef GS_EXPERIMENTS
-    // GS_MFMA_DEBUG (diagnostic timing builds, wrong results): kernel_lib.hpp k_mfma_rows DBG bits, C2 shape only
+    // GS_MFMA_DEBUG (diagnostic timing builds, wrong results): mfma_rows.hpp k_mfma_rows DBG bits, C2 shape only
     static const int mdbg = getenv("GS_MFMA_DEBUG") ? atoi(getenv("GS_MFMA_DEBUG")) : 0;
     if constexpr (CT == 2 && RT == 2 && LGKC == 9 && MAXA == 1) {
         if (gl == 2 && wct == 6 && mdbg == 1) kern = gsk::k_mfma_rows<CT, RT, LGKC, MAXA, false, 2, 3, 6, 1>;

@@ -34,7 +34,7 @@ a = np.frombuffer(st, dtype=np.uint64).reshape(nb, 64).astype(np.int64)
 nc = (info["lds_chunks"] + info["ksplit"] - 1) // info["ksplit"]
 t0 = a[:, [0]]
 out = {"total_med": float(np.median(a[:, 63] - a[:, 0])), "total_max": float((a[:, 63] - a[:, 0]).max())}
-# slot layout (kernel_lib.hpp k_mfma_rows STAMPS): role r (0 compute, 1 B rows, 2 entries) in
+# slot layout (mfma_rows.hpp k_mfma_rows STAMPS): role r (0 compute, 1 B rows, 2 entries) in
 # slots 21r..21r+20: 0 start, 1 chunk 0 staged, 2+2j chunk j's work done, 3+2j after its barrier
 for name, r in (("compute", 0), ("bload", 1), ("aload", 2)):
     base = 21 * r

@@ -325,6 +325,24 @@ def test_generate_program_new_families_compile(tmp_path, name, p0, p1):
                            "kernel_file.hip", "-o", "kernel_file.o"], cwd=d)
 
 
+_HIP_CODE = os.path.join(os.path.dirname(gsa.__file__), "csrc", "hip_code")
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not installed")
+@pytest.mark.parametrize("hdr", sorted(f for f in os.listdir(_HIP_CODE) if f.endswith(".hpp")))
+def test_hip_code_header_compiles_alone(hdr):
+    """every hip_code/ header is self-contained: it passes a device-side syntax check on its own with
+    the Makefile's HIPFLAGS, as the default build and as the experiments build sees it; host_layouts.hpp,
+    which emitted programs and the host code share, is also plain C++"""
+    import subprocess
+    hip = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result",
+           "-D__HIP_PLATFORM_AMD__", "--cuda-device-only", "-fsyntax-only", "-x", "hip"]
+    subprocess.check_call(hip + [hdr], cwd=_HIP_CODE)
+    subprocess.check_call(hip + ["-DGS_EXPERIMENTS", hdr], cwd=_HIP_CODE)
+    if hdr == "host_layouts.hpp":
+        subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", hdr], cwd=_HIP_CODE)
+
+
 def test_synthetic_generators_shapes():
     r, c, v = ds.pruned_weight(64, 48, 0.7, 13)
     assert len(r) == round(0.3 * 64 * 48) and np.all(np.diff(r.astype(np.int64)) >= 0)
