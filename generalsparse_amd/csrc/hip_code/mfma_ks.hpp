@@ -58,15 +58,26 @@ __device__ constexpr int vmcnt_imm() {
 // P8 (KS_POS8, device_layout.cc pos8_step): tP holds 8 bytes per group -- byte e = bit e of the
 // group's 8 x 16 segment id in bit 7, the entry's (row % 8) << 4 | column % 16 below; the image
 // halfword of a segment sg's entry is 384 * (sg >> 1) + 16 * (sg & 1) + 48 * (b >> 4) + (b & 15)
+// PF, the position form of a group: kKsPosU16 (8 x u16 image halfword), kKsPos8 (P8 above) or
+// kKsPosWin (KS_WPOS, device_layout.cc wpos_step): tP holds 8 bytes per group and tW one byte per
+// group -- the group's window w of the image (rows [5w, 5w + 5): halfwords [240w, 240w + 240)); byte e
+// of tP is entry e's halfword inside the window, so an entry's LDS address is (img + 480 w) + 2 * byte:
+// one base per group and two VALU per entry, kept for the clearing pass
 // ET (f16 or bf16, GS_BF16 plans): the element type of A's values, B and C.  The kernel moves
 // 16-bit words whatever they hold; ET selects the MFMA (mfma_elem) and the store conversion only
-template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, bool P8 = false, int NTL = 0, class ET = f16>
+// GS_KS_FULL_TILE (1; 0 in a variant build for the A/B): the step loop's fast iterations, see ks_body
+#ifndef GS_KS_FULL_TILE
+#define GS_KS_FULL_TILE 1
+#endif
+enum : int { kKsPosU16 = 0, kKsPos8 = 1, kKsPosWin = 2 };
+template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, int PF = kKsPosU16, int NTL = 0, class ET = f16>
 __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_row, const u32x4 *__restrict__ tP,
                                         const u32x4 *__restrict__ tV, const u32x2 *__restrict__ steps,
                                         const ET *__restrict__ B, ET *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
                                         uint32_t NS, uint32_t nwg, uint32_t row_base, float *__restrict__ slabs,
                                         uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps, uint32_t bx,
-                                        uint32_t prio) {
+                                        uint32_t prio, const uint8_t *__restrict__ tW = nullptr) {
+    constexpr bool P8 = PF == kKsPos8, WP = PF == kKsPosWin;
     constexpr uint32_t RB = 32 * CT;  // bytes per LDS B row (a 16*CT-column tile)
     constexpr uint32_t UB = 2 * CT;   // 16-B units per B row
     constexpr uint32_t IMG = ks_image_bytes<RT>();
@@ -94,10 +105,11 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     // its groups, so the groups' addresses wait on a load issued a round earlier
     const uint32_t nsw = NS > wv ? (NS - wv + W - 1u) / W : 0u;
     const size_t ubase = (size_t)u * NS;
-    using PV = typename std::conditional<P8, u32x2, u32x4>::type;
+    using PV = typename std::conditional<P8 || WP, u32x2, u32x4>::type;
     const PV *tPp = reinterpret_cast<const PV *>(tP);
     PV P[D][MAXG];
     u32x4 V[D][MAXG], BR[D][CT];
+    uint32_t WN[D][MAXG];  // WP: the groups' window bytes
     u32x2 NX[D];      // per slot: record of the step the slot loads next
     uint32_t CN[D];   // per slot: group count of the step whose groups it holds
     // the record is read by a vector load (vmcnt, in order with the groups): a scalar load
@@ -113,9 +125,20 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     // load form as a live step, so no path of the loop issues a different count).  The B rows
     // of a step need no record: they are issued apart from (and, in the prologue, before) the
     // groups, whose addresses wait for the step's record
-    auto load_b = [&](uint32_t i, u32x4 (&B_)[CT]) {
+    // FAST (the loop's fast iterations, below): all 32 rows of the step lie below K and the column
+    // tile is full, so the address is a scalar row term plus the lane's offset inside a step
+    uint32_t boff[CT];
+#pragma unroll
+    for (int c = 0; c < CT; c++) boff[c] = ((lane + 64u * c) / UB) * N + ((lane + 64u * c) % UB) * 8u;
+    auto load_b = [&](auto fast, uint32_t i, u32x4 (&B_)[CT]) {
         const uint32_t st = __builtin_amdgcn_readfirstlane(i < nsw ? wv + i * W : 0u);
         const uint32_t kr = k0 + st * 32u;  // first B row of the step
+        if constexpr (decltype(fast)::value) {
+            const ET *Bk = B + (size_t)kr * N + col0;
+#pragma unroll
+            for (int c = 0; c < CT; c++) B_[c] = ld_once_if<(NTL & 2) != 0>(reinterpret_cast<const u32x4 *>(Bk + boff[c]));
+            return;
+        }
 #pragma unroll
         for (int c = 0; c < CT; c++) {
             const uint32_t un = lane + 64u * c;  // 16-B unit of the step's 32 rows
@@ -128,7 +151,7 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     };
     // the groups of step i (b0: first group, gc: count), then the record of step i + D
     auto load_g_at = [&](uint32_t i, uint32_t b0, uint32_t gc, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG],
-                         u32x4 (&V_)[MAXG]) {
+                         u32x4 (&V_)[MAXG], uint32_t (&W_)[MAXG]) {
         CN_ = gc;
         NX_ = rec_of(i + D);
 #pragma unroll
@@ -137,10 +160,11 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
             const size_t at = (size_t)b0 + (qg < gc ? qg : 0u);
             P_[j] = ld_once_if<(NTL & 1) != 0>(tPp + at);
             V_[j] = ld_once_if<(NTL & 1) != 0>(tV + at);
+            if constexpr (WP) W_[j] = ld_once_if<(NTL & 1) != 0>(tW + at);
         }
     };
-    auto load_g = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG]) {
-        load_g_at(i, __builtin_amdgcn_readfirstlane(NX_[0]), __builtin_amdgcn_readfirstlane(NX_[1]), NX_, CN_, P_, V_);
+    auto load_g = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG], uint32_t (&W_)[MAXG]) {
+        load_g_at(i, __builtin_amdgcn_readfirstlane(NX_[0]), __builtin_amdgcn_readfirstlane(NX_[1]), NX_, CN_, P_, V_, W_);
     };
     // head steps (device_layout.cc ks_tiles::GH, prio bits 8..17): the first D steps of every wave
     // sit at (unit * min(W * D, NS) + step) * GH, padded with zero-row groups, so the prologue issues their
@@ -148,21 +172,21 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     const uint32_t GH = (prio >> 8) & 0x3ffu;
     if (GH) {
 #pragma unroll
-        for (int d = 0; d < D; d++) load_b((uint32_t)d, BR[d]);
+        for (int d = 0; d < D; d++) load_b(std::false_type{}, (uint32_t)d, BR[d]);
 #pragma unroll
         for (int d = 0; d < D; d++) {
             const uint32_t st = (uint32_t)d < nsw ? wv + (uint32_t)d * W : 0u;
-            load_g_at((uint32_t)d, (u * min((uint32_t)(W * D), NS) + st) * GH, GH, NX[d], CN[d], P[d], V[d]);
+            load_g_at((uint32_t)d, (u * min((uint32_t)(W * D), NS) + st) * GH, GH, NX[d], CN[d], P[d], V[d], WN[d]);
         }
         for (uint32_t x = lane; x < IMG / 16u; x += 64u) *reinterpret_cast<u32x4 *>(img + x * 16u) = zero4;
     } else {
 #pragma unroll
         for (int d = 0; d < D; d++) NX[d] = rec_of((uint32_t)d);
 #pragma unroll
-        for (int d = 0; d < D; d++) load_b((uint32_t)d, BR[d]);
+        for (int d = 0; d < D; d++) load_b(std::false_type{}, (uint32_t)d, BR[d]);
         for (uint32_t x = lane; x < IMG / 16u; x += 64u) *reinterpret_cast<u32x4 *>(img + x * 16u) = zero4;
 #pragma unroll
-        for (int d = 0; d < D; d++) load_g((uint32_t)d, NX[d], CN[d], P[d], V[d]);
+        for (int d = 0; d < D; d++) load_g((uint32_t)d, NX[d], CN[d], P[d], V[d], WN[d]);
     }
     GS_KS_STAMP(1u);
 
@@ -195,7 +219,8 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
             return 0u;
         }
     };
-    auto step = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG], u32x4 (&B_)[CT]) {
+    auto step = [&](auto fast, uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG], u32x4 (&B_)[CT],
+                    uint32_t (&W_)[MAXG]) {
         const bool live = i < nsw;  // wave-uniform
         const uint32_t gc = CN_;
         typedef typename mfma_elem<ET>::frag frag;
@@ -206,8 +231,20 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
 #pragma unroll
             for (int c = 0; c < CT; c++) {
                 const uint32_t un = lane + 64u * c, k = un / UB, s = un % UB;
-                *reinterpret_cast<u32x4 *>(bst + k * RB + b_piece<CT>(k, s >> 1) * 32u + (s & 1u) * 16u) =
-                    kr + k < K && s * 8u < nv ? B_[c] : zero4;
+                u32x4 b = B_[c];
+                if constexpr (!decltype(fast)::value) b = kr + k < K && s * 8u < nv ? b : zero4;
+                *reinterpret_cast<u32x4 *>(bst + k * RB + b_piece<CT>(k, s >> 1) * 32u + (s & 1u) * 16u) = b;
+            }
+            // WP: the entries' LDS addresses, once for the scatter and the clearing pass (lanes past
+            // the step's groups hold its first group: addresses inside the image all the same)
+            unsigned char *wa[WP ? MAXG : 1][8];
+            if constexpr (WP) {
+#pragma unroll
+                for (int j = 0; j < MAXG; j++) {
+                    unsigned char *wb = img + W_[j] * 480u;
+#pragma unroll
+                    for (int e = 0; e < 8; e++) wa[j][e] = wb + 2u * ((P_[j][e >> 2] >> (8 * (e & 3))) & 0xffu);
+                }
             }
             // scatter the step's entries into the image
 #pragma unroll
@@ -216,9 +253,13 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
                     const uint32_t hb = grp_hb(P_[j]);
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
-                        const uint32_t h = ent_h(P_[j], hb, e);
                         const uint16_t v = (uint16_t)((V_[j][e >> 1] >> (16 * (e & 1))) & 0xffffu);
-                        *reinterpret_cast<uint16_t *>(img + h * 2u) = v;
+                        if constexpr (WP) {
+                            *reinterpret_cast<uint16_t *>(wa[j][e]) = v;
+                        } else {
+                            const uint32_t h = ent_h(P_[j], hb, e);
+                            *reinterpret_cast<uint16_t *>(img + h * 2u) = v;
+                        }
                     }
                 }
             }
@@ -243,12 +284,15 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
                 if (lane + 64u * j < gc) {
                     const uint32_t hb = grp_hb(P_[j]);
 #pragma unroll
-                    for (int e = 0; e < 8; e++) *reinterpret_cast<uint16_t *>(img + ent_h(P_[j], hb, e) * 2u) = (uint16_t)0;
+                    for (int e = 0; e < 8; e++) {
+                        if constexpr (WP) *reinterpret_cast<uint16_t *>(wa[j][e]) = (uint16_t)0;
+                        else *reinterpret_cast<uint16_t *>(img + ent_h(P_[j], hb, e) * 2u) = (uint16_t)0;
+                    }
                 }
             }
         }
-        load_b(i + D, B_);
-        load_g(i + D, NX_, CN_, P_, V_);
+        load_b(fast, i + D, B_);
+        load_g(i + D, NX_, CN_, P_, V_, W_);
         if (live) {
 #pragma unroll
             for (int rt = 0; rt < RT; rt++)
@@ -263,9 +307,26 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     // first half of its steps
     const bool young = wv >= W / 2u;
     if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(1);
-    for (uint32_t i0 = 0; i0 < nsw; i0 += D) {
+    // Fast iterations: every k-step an iteration runs or loads for has its 32 B rows below K, on a full
+    // column tile -- the B rows are stored without the zero selects and loaded at a scalar row term +
+    // the lane's offset.  Only the last K range of a K that is no multiple of 32 has a short step, the
+    // last one; its waves run their last iterations in the general form.  fsp: the range's full steps
+    // (step st is full when st < fsp); a step past the wave's last reads step 0
+    const uint32_t fsp = min(NS, K > k0 ? (K - k0) / 32u : 0u);
+    const uint32_t nfull = fsp > wv ? (fsp - wv + W - 1u) / W : 0u;  // this wave's full steps
+    uint32_t fast_end = 0;
+    if (GS_KS_FULL_TILE && nv == 16u * CT)
+        fast_end = fsp == NS ? nsw : (nfull >= 2u * D ? ((nfull - 2u * D) / D + 1u) * D : 0u);
+    fast_end = __builtin_amdgcn_readfirstlane(fast_end);
+    uint32_t i0 = 0;
+    for (; i0 < fast_end; i0 += D) {
 #pragma unroll
-        for (int d = 0; d < D; d++) step(i0 + d, NX[d], CN[d], P[d], V[d], BR[d]);
+        for (int d = 0; d < D; d++) step(std::true_type{}, i0 + d, NX[d], CN[d], P[d], V[d], BR[d], WN[d]);
+        if ((prio & 3u) == 2u && young && i0 + D >= nsw / 2u && i0 < nsw / 2u) __builtin_amdgcn_s_setprio(0);
+    }
+    for (; i0 < nsw; i0 += D) {
+#pragma unroll
+        for (int d = 0; d < D; d++) step(std::false_type{}, i0 + d, NX[d], CN[d], P[d], V[d], BR[d], WN[d]);
         if ((prio & 3u) == 2u && young && i0 + D >= nsw / 2u && i0 < nsw / 2u) __builtin_amdgcn_s_setprio(0);
     }
     if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(0);
@@ -398,19 +459,20 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
 #undef GS_KS_STAMP
 }
 
-template <int CT, int RT, int W, int D, int MAXG, bool STAMPS = false, bool AP = true, bool P8 = false, int NTL = 0, class ET = f16>
+template <int CT, int RT, int W, int D, int MAXG, bool STAMPS = false, bool AP = true, int PF = kKsPosU16, int NTL = 0, class ET = f16>
 __global__ __launch_bounds__(64 * W) void k_mfma_ks(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
-                                                    const u32x4 *__restrict__ tP,  // 8 x u16 position per group
+                                                    const u32x4 *__restrict__ tP,  // 8 x u16 position per group (PF)
                                                     const u32x4 *__restrict__ tV,  // 8 x 16-bit value (ET) per group
                                                     const u32x2 *__restrict__ steps,  // per (unit, k-step): first group, count
                                                     const ET *__restrict__ B, ET *__restrict__ C, uint32_t K,
                                                     uint32_t N, uint32_t S, uint32_t NS, uint32_t nwg,
                                                     uint32_t row_base, float *__restrict__ slabs,
                                                     uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps = nullptr,
-                                                    uint32_t prio = 0) {
+                                                    uint32_t prio = 0,
+                                                    const uint8_t *__restrict__ tW = nullptr) {  // kKsPosWin: window byte per group
     // nwg == gridDim.x (an argument: kernarg preload)
-    ks_body<CT, RT, W, D, MAXG, STAMPS, AP, P8, NTL, ET>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nwg, row_base, slabs,
-                                                    arrivals, stamps, blockIdx.x, prio);
+    ks_body<CT, RT, W, D, MAXG, STAMPS, AP, PF, NTL, ET>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nwg, row_base, slabs,
+                                                    arrivals, stamps, blockIdx.x, prio, tW);
 }
 
 #ifdef GS_EXPERIMENTS
@@ -440,7 +502,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_persist(const uint32_t *__re
     while (u < nunits) {
         uint32_t pulled = 0;
         if (threadIdx.x == 0) pulled = __hip_atomic_fetch_add(queue + qx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ks_body<CT, RT, W, D, MAXG, false, true, false, NTL>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nunits,
+        ks_body<CT, RT, W, D, MAXG, false, true, kKsPosU16, NTL>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nunits,
                                                           row_base, slabs, arrivals, nullptr, u, prio);
         __syncthreads();
         if (threadIdx.x == 0) next_sh = pulled;
@@ -479,8 +541,10 @@ struct ks_entry {  // 96 B
     void *C;
     float *slabs;
     uint32_t *arrivals;
-    uint32_t K, S, NS, nwg, row_base, pad0, pad1, pad2;
+    uint32_t K, S, NS, nwg, row_base, pad0;  // pad0: the entry's head-step group count
+    const uint8_t *tW;  // kKsPosWin: window byte per group
 };
+static_assert(sizeof(ks_entry) == 96, "ks_entry is 96 bytes");
 // kKsGroupMax: kernel_consts.hpp
 struct ks_group_args {
     uint32_t begin[kKsGroupMax + 1];  // first workgroup of each entry (+ the total)
@@ -488,7 +552,7 @@ struct ks_group_args {
     ks_entry e[kKsGroupMax];
 };
 
-template <int CT, int RT, int W, int D, int MAXG, bool P8 = false, bool AP = true, int NTL = 0, class ET = f16>
+template <int CT, int RT, int W, int D, int MAXG, int PF = kKsPosU16, bool AP = true, int NTL = 0, class ET = f16>
 __global__ __launch_bounds__(64 * W) void k_mfma_ks_group(ks_group_args args) {
     const uint32_t bx = blockIdx.x, n = args.n;
     uint32_t sel = 0;
@@ -498,9 +562,9 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_group(ks_group_args args) {
     sel = __builtin_amdgcn_readfirstlane(sel);
     const ks_entry &e = args.e[sel];  // kernel arguments: scalar loads at a computed offset
     if (bx - args.begin[sel] >= e.nwg) return;  // padding up to the next entry's multiple of 8
-    ks_body<CT, RT, W, D, MAXG, false, AP, P8, NTL, ET>(e.tbr, e.tP, e.tV, e.steps, (const ET *)e.B, (ET *)e.C, e.K, args.N, e.S, e.NS,
+    ks_body<CT, RT, W, D, MAXG, false, AP, PF, NTL, ET>(e.tbr, e.tP, e.tV, e.steps, (const ET *)e.B, (ET *)e.C, e.K, args.N, e.S, e.NS,
                                                    e.nwg, e.row_base, e.slabs, e.arrivals, nullptr, bx - args.begin[sel],
-                                                   args.pad[0] | (e.pad0 << 8));
+                                                   args.pad[0] | (e.pad0 << 8), e.tW);
 }
 
 }  // namespace gsk

@@ -254,8 +254,10 @@ std::string matrix_core_source(const meta_data_set &m, const mc_layout &L, int r
         const uint64_t nb = L.tbr.size() - 1, nwg = nb * t.S;
         o << "    auto tbr = rd(\"TBLOCK_META_first_row_indices_0\");\n"
           << "    std::vector<uint32_t> t32(tbr.begin(), tbr.end()); uint32_t *d_tbr = up(t32);\n"
-          << (t.P8 ? "    uint8_t *d_pos = up(rdb<uint8_t>(\"TBLOCK_META_mfma_ks_entry_pos_0.bin\"));  // 8-bit positions\n"
-                   : "    uint16_t *d_pos = up(rdb<uint16_t>(\"TBLOCK_META_mfma_ks_entry_pos_0.bin\"));\n")
+          << (t.WP ? "    uint8_t *d_pos = up(rdb<uint8_t>(\"TBLOCK_META_mfma_ks_entry_pos_0.bin\"));  // positions inside the group's window\n"
+                     "    uint8_t *d_win = up(rdb<uint8_t>(\"TBLOCK_META_mfma_ks_group_win_0.bin\"));  // window byte per group\n"
+              : t.P8 ? "    uint8_t *d_pos = up(rdb<uint8_t>(\"TBLOCK_META_mfma_ks_entry_pos_0.bin\"));  // 8-bit positions\n"
+                     : "    uint16_t *d_pos = up(rdb<uint16_t>(\"TBLOCK_META_mfma_ks_entry_pos_0.bin\"));\n")
           << "    uint16_t *d_val = up(rdb<uint16_t>(\"TBLOCK_META_mfma_ks_entry_val_0.bin\"));\n"
           << "    uint32_t *d_steps = up(rdb<uint32_t>(\"TBLOCK_META_mfma_ks_steps_0.bin\"));\n"
           << "    // the tagged slabs start (and are left by every launch) all 0\n"
@@ -265,7 +267,8 @@ std::string matrix_core_source(const meta_data_set &m, const mc_layout &L, int r
           << "ull + 4);\n";
         const std::string k = "gsk::k_mfma_ks<" + std::to_string(CT) + ", " + std::to_string(t.RT) + ", " +
                               std::to_string(t.W) + ", " + std::to_string(kKsDepth) + ", " + std::to_string(t.MAXG) +
-                              std::string(", false, ") + (t.AP ? "true" : "false") + ", " + (t.P8 ? "true" : "false") +
+                              std::string(", false, ") + (t.AP ? "true" : "false") + ", " +
+                              (t.WP ? "gsk::kKsPosWin" : t.P8 ? "true" : "false") +  // (false / true: kKsPosU16 / kKsPos8)
                               (t.NT ? ", " + std::to_string(t.NT) + ">" : ">");
         setup = "hipFuncSetAttribute((const void *)" + k + ", hipFuncAttributeMaxDynamicSharedMemorySize, " +
                 std::to_string(t.lds_bytes) + ")";
@@ -273,7 +276,7 @@ std::string matrix_core_source(const meta_data_set &m, const mc_layout &L, int r
                  std::to_string(64 * t.W) + ", " + std::to_string(t.lds_bytes) +
                  ">>>(d_tbr, (const gsk::u32x4 *)d_pos, (const gsk::u32x4 *)d_val, (const gsk::u32x2 *)d_steps, d_B, d_C, "
                  "(uint32_t)K, N, " + std::to_string(t.S) + "u, " + std::to_string(t.NS) + "u, " + std::to_string(nwg) + "u, 0u, d_ws, d_arr, nullptr, " +
-                 std::to_string((uint32_t)get_config().KS_PRIO | (t.GH << 8)) + "u)";
+                 std::to_string((uint32_t)get_config().KS_PRIO | (t.GH << 8)) + (t.WP ? "u, d_win)" : "u)");
     } else if (L.kind == mc_layout::BM) {
         const bm_tiles &t = L.bm;
         const uint64_t nb = L.tbr.size() - 1, nwg = nb * t.S;
@@ -613,7 +616,9 @@ uint64_t code_generator::generate_final_program(int repeat, const std::string &r
     uint64_t id = meta->output_format_to_dir(root, spec.arrays, &dir);
     const mc_layout L = emitted_layout(*meta, spec, sub);
     if (L.kind == mc_layout::KS) {
-        if (L.ks.P8)
+        if (L.ks.WP)
+            write_bin(dir + "/TBLOCK_META_mfma_ks_group_win_0.bin", L.ks.win);
+        if (L.ks.P8 || L.ks.WP)
             write_bin(dir + "/TBLOCK_META_mfma_ks_entry_pos_0.bin", L.ks.pos8);
         else
             write_bin(dir + "/TBLOCK_META_mfma_ks_entry_pos_0.bin", L.ks.pos);

@@ -2,6 +2,7 @@
 #include "device_layout.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cstring>
 
 namespace gs {
@@ -222,6 +223,72 @@ static size_t pos8_step(const std::vector<uint16_t> &row, const std::vector<uint
     return groups;
 }
 
+// KS_WPOS layout of one k-step (k_mfma_ks with kKsPosWin).  Window w of the wave image is its rows
+// [5w, 5w + 5) -- halfwords [240w, 240w + 240) at the 48-halfword row stride -- so an entry's place
+// inside its window is one byte, (row % 5) * 48 + column.  Every group of 8 entries lies in ONE
+// window: 8 position bytes + 8 values + one window byte, 25 B against 32 B with u16 positions; each
+// window rounds up to whole groups.  A window's last group is padded with copies of that group's
+// first entry (the same value written twice to one place: the scatter and the clear are
+// idempotent).  The groups follow the windows in ascending order; group G of the step is written
+// by lane G % 64, so the groups [32h, 32h + 32) share a half-wave, and slot e of a window's groups
+// takes entries on LDS write banks ((halfword / 2) % 32) that slot e of that half's earlier groups
+// -- of this window and of the ones before it -- has not used, fullest banks first; a bank twice
+// only when nothing else is left.  Appends to out_pos8 / out_win / out_val; returns the groups.
+constexpr uint32_t kKsWinRows = 5;
+static size_t wpos_step(const std::vector<uint16_t> &row, const std::vector<uint16_t> &colw,
+                        const std::vector<uint16_t> &hv, uint32_t RS, std::vector<uint8_t> &out_pos8,
+                        std::vector<uint8_t> &out_win, std::vector<uint16_t> &out_val) {
+    const size_t n = row.size();
+    uint32_t nwin = 0;
+    for (size_t i = 0; i < n; i++) nwin = std::max<uint32_t>(nwin, row[i] / kKsWinRows + 1u);
+    std::vector<std::vector<uint32_t>> win(nwin);
+    for (uint32_t i = 0; i < n; i++) win[row[i] / kKsWinRows].push_back(i);
+    size_t groups = 0;
+    std::vector<std::array<uint32_t, 8>> used;  // per half-wave of groups and slot: banks taken
+    std::vector<std::vector<uint32_t>> bucket(32);
+    std::vector<uint32_t> slot;
+    for (uint32_t w = 0; w < nwin; w++) {
+        const auto &es = win[w];
+        if (es.empty()) continue;
+        GS_CHECK(w < 256, "KS_WPOS: window beyond 8 bits");
+        const size_t ng = (es.size() + 7) / 8;
+        for (auto &b : bucket) b.clear();
+        for (uint32_t i : es) bucket[((uint32_t)row[i] * RS + colw[i]) / 2 % 32].push_back(i);
+        used.resize((groups + ng + 31) / 32, std::array<uint32_t, 8>{});
+        slot.assign(ng * 8, UINT32_MAX);
+        size_t left = es.size();
+        for (int e = 0; e < 8 && left; e++)
+            for (size_t l = 0; l < ng && left; l++) {
+                uint32_t &mask = used[(groups + l) / 32][e];
+                int best = -1, any = -1;
+                for (int k = 0; k < 32; k++) {
+                    if (bucket[k].empty()) continue;
+                    if (any < 0 || bucket[k].size() > bucket[any].size()) any = k;
+                    if (!((mask >> k) & 1u) && (best < 0 || bucket[k].size() > bucket[best].size())) best = k;
+                }
+                const int k = best >= 0 ? best : any;
+                slot[l * 8 + e] = bucket[k].back();
+                bucket[k].pop_back();
+                mask |= 1u << k;
+                left--;
+            }
+        for (size_t gi = 0; gi < ng; gi++) {
+            const uint32_t first = slot[gi * 8];
+            GS_CHECK(first != UINT32_MAX, "KS_WPOS: a group without entries");
+            for (int e = 0; e < 8; e++) {
+                const uint32_t i = slot[gi * 8 + e] == UINT32_MAX ? first : slot[gi * 8 + e];
+                const uint32_t code = (row[i] % kKsWinRows) * RS + colw[i];
+                GS_CHECK(code < kKsWinRows * RS && kKsWinRows * RS <= 256, "KS_WPOS: position beyond its window");
+                out_pos8.push_back((uint8_t)code);
+                out_val.push_back(hv[i]);
+            }
+            out_win.push_back((uint8_t)w);
+        }
+        groups += ng;
+    }
+    return groups;
+}
+
 bool build_mfma_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                       const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,
                       size_t lds_budget, int64_t max_fill, mfma_tiles &t, std::string &why) {
@@ -357,11 +424,21 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
     // KS_POS8 (8-bit positions in 8 x 16 segments; N = 32, RT <= 8: segment ids < 32)
     t.P8 = get_config().KS_POS8 && CT == 2 && (W == kKsWaves || W == 4);
     t.NT = (CT == 2 || CT == 8) && (W == kKsWaves || W == 12) && !t.P8 && t.AP && get_config().KS_NT ? 1u : 0u;
-    // pass 1: the largest step (entries of a row block in 32 columns; P8: groups per segment)
+    // KS_WPOS (one-byte positions in 5-row windows; fp16 at N = 32 on 8 waves with the apart layout):
+    // other dense widths keep the u16 layout, the variants the kernel is not built for refuse
+    if (get_config().KS_WPOS && CT == 2) {
+        if (dtype != kF16) throw gs_error("KS_WPOS: window positions are an fp16 layout (bf16 plans take the u16 positions)", -2);
+        if (W != kKsWaves || !t.AP || t.P8 || get_config().KS_PERSIST > 0)
+            throw gs_error("KS_WPOS: window positions are built for 8 waves, the apart LDS layout and the static grid "
+                           "(not with KS_WAVES, KS_APART = 0, KS_POS8 or KS_PERSIST)", -2);
+        t.WP = true;
+    }
+    // pass 1: the largest step (entries of a row block in 32 columns; P8: groups per segment, WP: per window)
     uint64_t gmax = 1;
+    const uint32_t nwn = (16 * RT + kKsWinRows - 1) / kKsWinRows;  // WP: windows holding entries
     {
-        const uint32_t nsg = 4 * RT;
-        std::vector<uint32_t> cnt((size_t)((K + 31) / 32) * (t.P8 ? nsg : 1u));
+        const uint32_t nsg = t.WP ? nwn : 4 * RT;
+        std::vector<uint32_t> cnt((size_t)((K + 31) / 32) * (t.P8 || t.WP ? nsg : 1u));
         for (uint64_t g = 0; g < nb; g++) {
             std::fill(cnt.begin(), cnt.end(), 0u);
             for (uint64_t r = tb_rows[g]; r < tb_rows[g + 1]; r++)
@@ -369,10 +446,12 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
                     const uint64_t st = col[e] / 32;
                     if (t.P8)
                         cnt[st * nsg + ((r - tb_rows[g]) / 8) * 2 + (col[e] % 32) / 16]++;
+                    else if (t.WP)
+                        cnt[st * nsg + (r - tb_rows[g]) / kKsWinRows]++;
                     else
                         cnt[st]++;
                 }
-            if (t.P8) {
+            if (t.P8 || t.WP) {
                 for (size_t st = 0; st < cnt.size() / nsg; st++) {
                     uint64_t ngs = 0;
                     for (uint32_t k = 0; k < nsg; k++) ngs += (cnt[st * nsg + k] + 7) / 8;
@@ -413,13 +492,16 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
     const uint32_t HS = std::min<uint32_t>(W * kKsDepth, t.NS);  // head slots per unit
     if (!t.P8 && get_config().KS_HEAD) {
         uint64_t gh = 1, head_groups = 0, all_groups = 0;
-        std::vector<uint32_t> c2((size_t)S * t.NS);
+        const uint32_t nsg = t.WP ? nwn : 1u;  // (WP: a step's groups are its windows' groups)
+        std::vector<uint32_t> c2((size_t)S * t.NS * nsg);
         for (uint64_t g = 0; g < nb; g++) {
             std::fill(c2.begin(), c2.end(), 0u);
             for (uint64_t r = tb_rows[g]; r < tb_rows[g + 1]; r++)
-                for (uint64_t e = row_ptr[r]; e < row_ptr[r + 1]; e++) c2[col[e] / 32]++;
-            for (size_t st = 0; st < c2.size(); st++) {
-                const uint64_t ng = (c2[st] + 7) / 8;
+                for (uint64_t e = row_ptr[r]; e < row_ptr[r + 1]; e++)
+                    c2[col[e] / 32 * nsg + (t.WP ? (r - tb_rows[g]) / kKsWinRows : 0u)]++;
+            for (size_t st = 0; st < c2.size() / nsg; st++) {
+                uint64_t ng = 0;
+                for (uint32_t k = 0; k < nsg; k++) ng += (c2[st * nsg + k] + 7) / 8;
                 all_groups += ng;
                 if (st % t.NS < HS) {
                     head_groups += ng;
@@ -438,16 +520,25 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
     }
     const uint32_t RS = gsk::kKsStride / 2;  // halfwords per image row
     const uint32_t pad_h = 16 * RT * RS;      // the zero row
-    if (t.P8)
-        t.pos8.reserve(row_ptr[tb_rows[nb]] - row_ptr[tb_rows[0]] + (size_t)nb * S * t.NS * 8 * RT + 8);
+    // WP: the zero row's window and its first halfword inside it; an all-padding group (a head slot's
+    // spare groups, the spare group) writes 0 there, its 8 entries on banks of their own
+    const uint32_t zwin = 16 * RT / kKsWinRows, zcode = (16 * RT % kKsWinRows) * RS;
+    if (t.P8 || t.WP)
+        t.pos8.reserve(row_ptr[tb_rows[nb]] - row_ptr[tb_rows[0]] + (size_t)nb * S * t.NS * 8 * (t.WP ? nwn : RT) + 8);
     else
         t.pos.reserve(row_ptr[tb_rows[nb]] - row_ptr[tb_rows[0]] + (size_t)nb * S * t.NS * 8 + 8);
-    t.val.reserve(t.P8 ? t.pos8.capacity() : t.pos.capacity());
+    t.val.reserve(t.P8 || t.WP ? t.pos8.capacity() : t.pos.capacity());
     t.steps.reserve((size_t)nb * S * t.NS * 2);
-    if (t.GH) {  // the head region first: every slot a zero-row group until its step fills it
+    if (t.GH && t.WP) {
+        t.pos8.resize((size_t)nb * S * HS * t.GH * 8);
+        for (size_t i = 0; i < t.pos8.size(); i++) t.pos8[i] = (uint8_t)(zcode + 2 * (i % 8));
+        t.win.assign((size_t)nb * S * HS * t.GH, (uint8_t)zwin);
+        t.val.assign(t.pos8.size(), 0);
+    } else if (t.GH) {  // the head region first: every slot a zero-row group until its step fills it
         t.pos.assign((size_t)nb * S * HS * t.GH * 8, (uint16_t)pad_h);
         t.val.assign(t.pos.size(), 0);
     }
+    std::vector<uint8_t> hpos8, hwin;
     std::vector<uint64_t> cur;
     std::vector<uint16_t> pos, hv, prow, pcol, hpos, hval;
     for (uint64_t g = 0; g < nb; g++) {
@@ -472,7 +563,20 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
                     cur[i] = e;
                 }
                 size_t before, ng;
-                if (t.GH && s < HS) {  // a head step: its fixed slot
+                if (t.WP && t.GH && s < HS) {  // a head step: its fixed slot
+                    hpos8.clear();
+                    hwin.clear();
+                    hval.clear();
+                    ng = wpos_step(prow, pcol, hv, RS, hpos8, hwin, hval);
+                    GS_CHECK(ng <= t.GH, "k_mfma_ks head step exceeds its slot");
+                    before = (((size_t)g * S + q) * HS + s) * t.GH * 8;
+                    std::copy(hpos8.begin(), hpos8.end(), t.pos8.begin() + before);
+                    std::copy(hwin.begin(), hwin.end(), t.win.begin() + before / 8);
+                    std::copy(hval.begin(), hval.end(), t.val.begin() + before);
+                } else if (t.WP) {
+                    before = t.pos8.size();
+                    ng = wpos_step(prow, pcol, hv, RS, t.pos8, t.win, t.val);
+                } else if (t.GH && s < HS) {  // a head step: its fixed slot
                     hpos.clear();
                     hval.clear();
                     bank_order_segment(pos, hv, pad_h, hpos, hval, RS / 2);
@@ -494,7 +598,10 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
                 t.steps.push_back((uint32_t)ng);
             }
     }
-    if (t.P8)
+    if (t.WP) {  // spare group: loads past a wave's last step
+        for (uint32_t e = 0; e < 8; e++) t.pos8.push_back((uint8_t)(zcode + 2 * e));
+        t.win.push_back((uint8_t)zwin);
+    } else if (t.P8)
         t.pos8.insert(t.pos8.end(), 8, (uint8_t)0);  // spare group: loads past a wave's last step (never scattered)
     else
         t.pos.insert(t.pos.end(), 8, (uint16_t)pad_h);  // spare group: loads past a wave's last step

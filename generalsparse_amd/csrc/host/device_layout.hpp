@@ -67,6 +67,10 @@ struct ks_tiles {
     uint32_t CT = 0;  // 16-column MFMA tiles per workgroup (ks_ct_rt)
     bool AP = true;   // partial tiles beside the stages (ks_red_apart; KS_APART)
     bool P8 = false;  // 8-bit positions (KS_POS8): pos8 instead of pos, see build_ks_tiles
+    // window positions (KS_WPOS; fp16, CT = 2, 8 waves, apart layout): pos8 holds 8 bytes per group, each
+    // an entry's halfword inside the group's window of the wave image, and win one byte per group,
+    // the window (image rows [5w, 5w + 5)); see build_ks_tiles
+    bool WP = false;
     uint32_t NT = 0;  // k_mfma_ks NTL: 1 = A's groups by non-temporal loads (KS_NT; N = 32, 8 waves, apart layout)
     // head steps (KS_HEAD): the first W x kKsDepth k-steps of every unit -- the ones each wave loads
     // in its prologue -- have their groups at a fixed place, (unit * HS + step) * GH with HS =
@@ -76,7 +80,8 @@ struct ks_tiles {
     uint32_t GH = 0;  // groups per head step (0: no head region)
     size_t lds_bytes = 0;
     std::vector<uint16_t> pos, val;  // 8 u16 per group each
-    std::vector<uint8_t> pos8;       // P8: 8 bytes per group
+    std::vector<uint8_t> pos8;       // P8 / WP: 8 bytes per group
+    std::vector<uint8_t> win;        // WP: one window byte per group
     std::vector<uint32_t> steps;     // per (unit, k-step): first group, group count
 };
 

@@ -120,7 +120,10 @@ struct config_t {
     int64_t KS_NT = 0;           // k_mfma_ks at N = 32: A's groups by non-temporal loads; a plan-search variant (C2
                                  // 13.8 -> 12.9 us, the headline layer 165.7 -> 167.8 us; B's rows as well: 14.1 us,
                                  // profiles/r05n_nt3.txt)
-    int64_t KS_HEAD = 1;         // k_mfma_ks: the head steps (each wave's first kKsDepth k-steps) at fixed, padded
+    int64_t KS_WPOS = 0;         // k_mfma_ks, fp16 at N = 32: one-byte entry positions inside 5-row windows of the wave
+                                 // image + one window byte per group (25 B per group of 8 instead of 32; every
+                                 // group lies in one window).  Other shapes keep the u16 layout
+    int64_t KS_HEAD = 1;        // k_mfma_ks: the head steps (each wave's first kKsDepth k-steps) at fixed, padded
                                  // places, loaded without their records (when the padding costs <= 6% more groups)
     int64_t KS_PERSIST = 0;      // k_mfma_ks: persistent grid size pulling (row block, K range) units (experiments build)
     int64_t MP_HUB_COLS = 0;     // MP_COL_PARTS = 2: partition 0 = this many densest columns (0: round-robin)

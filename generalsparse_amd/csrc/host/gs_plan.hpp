@@ -17,6 +17,7 @@ struct device_arrays {
     void *col = nullptr, *val = nullptr;
     void *pad_out = nullptr;  // row-padded plans: scratch output of all the plan's rows
     void *tcol = nullptr, *tval = nullptr;  // LDS tile layout (k_lds_rows)
+    void *tw = nullptr;  // k_mfma_ks with window positions (KS_WPOS): one window byte per group
     uint32_t *t0 = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *t4 = nullptr;
     uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;
     uint64_t *m0 = nullptr;
@@ -48,6 +49,7 @@ struct device_plan {
     uint32_t ks_ctw = 0;      // k_mfma_ks: 16-column tiles per workgroup (ks_tiles::CT)
     bool ks_ap = true;        // k_mfma_ks: partial tiles beside the stages (ks_tiles::AP)
     bool ks_p8 = false;       // k_mfma_ks: 8-bit entry positions (ks_tiles::P8, KS_POS8)
+    bool ks_wp = false;       // k_mfma_ks: one-byte window positions (ks_tiles::WP, KS_WPOS)
     uint32_t ks_gh = 0;       // k_mfma_ks: groups per head step (ks_tiles::GH; 0: every step by record)
     uint32_t ks_nt = 0;       // k_mfma_ks: non-temporal loads of A's groups (NTL bit 0; ks_tiles::NT, KS_NT)
     uint32_t ks_persist = 0;  // k_mfma_ks: persistent grid of this many workgroups pulling units (KS_PERSIST, experiments)

@@ -631,12 +631,15 @@ void upload_plan(plan_state &p, int dtype, int device) {
             d.ks_ctw = kt.CT;
             d.ks_ap = kt.AP;
             d.ks_p8 = kt.P8;
+            d.ks_wp = kt.WP;
             d.ks_nt = kt.NT;
             d.ks_gh = kt.GH;
             d.ks_persist = (uint32_t)std::max<int64_t>(0, get_config().KS_PERSIST);
             if (d.ks_persist) a.t3 = dev_copy(d, std::vector<uint32_t>(9, 0u));  // 8 XCD heads + the exit count
             a.t0 = dev_copy(d, to_u32(mc.tbr, "BMTB first_row_indices"));
-            a.tcol = kt.P8 ? (void *)dev_copy(d, kt.pos8) : (void *)dev_copy(d, kt.pos);
+            GS_CHECK(!(kt.WP && d.ks_persist), "KS_WPOS: window positions are not built for the persistent grid (KS_PERSIST)");
+            a.tcol = kt.P8 || kt.WP ? (void *)dev_copy(d, kt.pos8) : (void *)dev_copy(d, kt.pos);
+            if (kt.WP) a.tw = dev_copy(d, kt.win);
             a.tval = dev_copy(d, kt.val);
             a.t1 = dev_copy(d, kt.steps);
             d.bytes_tile = d.bytes_A - before;
@@ -1034,6 +1037,7 @@ void add_replica(plan_state &p) {
     r.m0 = (uint64_t *)dup(s.m0);
     r.tcol = dup(s.tcol);
     r.tval = dup(s.tval);
+    r.tw = dup(s.tw);
     r.t0 = (uint32_t *)dup(s.t0);
     r.t1 = (uint32_t *)dup(s.t1);
     r.t2 = (uint32_t *)dup(s.t2);

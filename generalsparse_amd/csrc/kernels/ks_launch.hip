@@ -58,6 +58,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
         GS_CHECK(d.waves == kKsWaves && !d.ks_p8 && d.ks_ap && !d.ks_persist,
                  "k_mfma_ks at bf16 is built for 8 waves, 16-bit positions and the apart LDS layout: the experiments "
                  "variants (KS_WAVES, KS_POS8, KS_APART = 0, KS_PERSIST) are fp16 kernels");
+        GS_CHECK(!d.ks_wp, "k_mfma_ks at bf16 is built for 16-bit positions: KS_WPOS is an fp16 layout");
     }
 #ifdef GS_EXPERIMENTS
     // KS_WAVES = 16 (fixed at upload): every instantiation spills (128 VGPRs at 4 waves per
@@ -86,7 +87,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
             hipLaunchKernelGGL(kd, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(64 * W), d.lds_bytes, s,
                                a.t0, (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C,
                                (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit, (uint32_t)d.row_base,
-                               a.ws, a.t2, stamps, ks_prio_arg());
+                               a.ws, a.t2, stamps, ks_prio_arg(), (const uint8_t *)nullptr);
             HIP_OK(hipGetLastError());
             return;
         }
@@ -97,14 +98,15 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
         if (d.waves == 4) {
             if constexpr (CT == 2) {
                 GS_CHECK(!d.ks_ap, "k_mfma_ks with 4 waves runs the overlapped LDS layout");
-                auto k4 = d.ks_p8 ? gsk::k_mfma_ks<CT, RT, 4, (int)kKsDepth, MAXG, false, false, true>
-                                  : gsk::k_mfma_ks<CT, RT, 4, (int)kKsDepth, MAXG, false, false, false>;
+                GS_CHECK(!d.ks_wp, "k_mfma_ks: window positions (KS_WPOS) are built for 8 waves");
+                auto k4 = d.ks_p8 ? gsk::k_mfma_ks<CT, RT, 4, (int)kKsDepth, MAXG, false, false, gsk::kKsPos8>
+                                  : gsk::k_mfma_ks<CT, RT, 4, (int)kKsDepth, MAXG, false, false, gsk::kKsPosU16>;
                 GS_CHECK(gsk::ks_lds_bytes(CT, RT, 4, false) <= d.lds_bytes, "k_mfma_ks: LDS size disagrees with the upload");
                 grant_lds(d.device, k4, d.lds_bytes);
                 hipLaunchKernelGGL(k4, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(256), d.lds_bytes,
                                    s, a.t0, (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B,
                                    C, (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit,
-                                   (uint32_t)d.row_base, a.ws, a.t2, stamps, ks_prio_arg() | (d.ks_gh << 8));
+                                   (uint32_t)d.row_base, a.ws, a.t2, stamps, ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)nullptr);
                 HIP_OK(hipGetLastError());
                 return;
             } else {
@@ -116,21 +118,31 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
     GS_CHECK(d.waves == kKsWaves && !d.ks_p8 && d.ks_ap,
              "k_mfma_ks with 4 or 16 waves, 8-bit positions or the overlapped LDS layout: experiments build");
 #endif
-    auto kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, STAMPS, true, false, 0, ET>;
+    auto kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, STAMPS, true, gsk::kKsPosU16, 0, ET>;
     if (d.ks_nt) {  // KS_NT: A's groups by non-temporal loads (N = 32 / 128, 8 waves, the apart layout)
         if constexpr ((CT == 2 || CT == 8) && (W == (int)kKsWaves || W == 12) && !STAMPS) {
             GS_CHECK(d.ks_ap && !d.ks_p8, "k_mfma_ks: non-temporal loads are built for the apart layout, 16-bit positions");
             GS_CHECK(d.ks_nt == 1, "k_mfma_ks: KS_NT is built for A's groups (1)");
-            kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, false, 1, ET>;
+            kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, gsk::kKsPosU16, 1, ET>;
         } else {
             throw gs_error("k_mfma_ks: non-temporal loads are built for N = 32 and 128-column tiles, 8 waves");
+        }
+    }
+    if (d.ks_wp) {  // KS_WPOS: one-byte window positions (fp16, N = 32, 8 waves, the apart layout)
+        if constexpr (F16 && CT == 2 && W == (int)kKsWaves && !STAMPS) {
+            GS_CHECK(d.ks_ap && !d.ks_p8 && !d.ks_persist && a.tw,
+                     "k_mfma_ks: window positions are built for the apart LDS layout and the static grid");
+            kern = d.ks_nt ? gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, gsk::kKsPosWin, 1>
+                           : gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, gsk::kKsPosWin, 0>;
+        } else {
+            throw gs_error("k_mfma_ks: window positions (KS_WPOS) are built for fp16, N = 32, 8 waves");
         }
     }
 #ifdef GS_EXPERIMENTS
     if (d.ks_p8) {  // KS_POS8: 8-bit entry positions (N = 32, 8 waves, the apart layout)
         if constexpr (F16 && CT == 2 && W == (int)kKsWaves && !STAMPS) {
             GS_CHECK(d.ks_ap, "k_mfma_ks: 8-bit positions are built with the apart LDS layout");
-            kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, true>;
+            kern = gsk::k_mfma_ks<CT, RT, W, (int)kKsDepth, MAXG, false, true, gsk::kKsPos8>;
         } else {
             throw gs_error("k_mfma_ks: 8-bit positions are built for N = 32, 8 waves");
         }
@@ -146,7 +158,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
     // KS_PERSIST (fixed at upload): a persistent grid of d.ks_persist workgroups pulling units
     if (d.ks_persist) {
         if constexpr (F16 && W == (int)kKsWaves && !STAMPS && (CT == 2 || CT == 8)) {
-            GS_CHECK(d.ks_ap && !d.ks_p8 && a.t3 && ks_col_tiles_ct(N, CT) == 1, "k_mfma_ks_persist: 8 waves, apart layout, one column tile");
+            GS_CHECK(d.ks_ap && !d.ks_p8 && !d.ks_wp && a.t3 && ks_col_tiles_ct(N, CT) == 1, "k_mfma_ks_persist: 8 waves, apart layout, 16-bit positions, one column tile");
             auto kp = d.ks_nt ? gsk::k_mfma_ks_persist<CT, RT, W, (int)kKsDepth, MAXG, 1>
                               : gsk::k_mfma_ks_persist<CT, RT, W, (int)kKsDepth, MAXG, 0>;
             grant_lds(d.device, kp, d.lds_bytes);
@@ -170,7 +182,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
     hipLaunchKernelGGL(kern, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(64 * W), d.lds_bytes, s, a.t0,
                        (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C,
                        (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit, (uint32_t)d.row_base, a.ws, a.t2, stamps,
-                       ks_prio_arg() | (d.ks_gh << 8));
+                       ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)a.tw);
     HIP_OK(hipGetLastError());
 }
 
@@ -333,16 +345,24 @@ void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStre
             return;
         }
     }
-    auto kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, AP, 0, ET>;
+    auto kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, gsk::kKsPosU16, AP, 0, ET>;
     if constexpr (F16) {
-        if (it[0].p->dev.ks_p8) kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, true, AP>;
+        if (it[0].p->dev.ks_p8) kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, gsk::kKsPos8, AP>;
     }
 #else
     GS_CHECK(!it[0].p->dev.ks_p8, "k_mfma_ks_group: 8-bit positions are an experiments-build layout");
-    auto kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, AP, 0, ET>;
+    auto kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, gsk::kKsPosU16, AP, 0, ET>;
 #endif
     if constexpr (AP) {
-        if (it[0].p->dev.ks_nt) kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, false, true, 1, ET>;
+        if (it[0].p->dev.ks_nt) kern = gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, gsk::kKsPosU16, true, 1, ET>;
+    }
+    if (it[0].p->dev.ks_wp) {  // KS_WPOS (ks_group_key: every entry of the group has the layout)
+        if constexpr (F16 && AP) {
+            kern = it[0].p->dev.ks_nt ? gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, gsk::kKsPosWin, true, 1>
+                                      : gsk::k_mfma_ks_group<2, RT, W, (int)kKsDepth, MAXG, gsk::kKsPosWin, true, 0>;
+        } else {
+            throw gs_error("k_mfma_ks_group: window positions (KS_WPOS) are built for fp16, 8 waves");
+        }
     }
     GS_CHECK(!it.empty() && it.size() <= (size_t)gsk::kKsGroupMax, "k_mfma_ks_group: 1..32 entries");
     gsk::ks_group_args args;
@@ -370,6 +390,8 @@ void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStre
         e.nwg = (uint32_t)d.n_rows_aux * d.ksplit;
         e.row_base = (uint32_t)d.row_base;
         e.pad0 = d.ks_gh;  // the entry's head-step group count (ks_body's prio bits 8..17)
+        GS_CHECK(d.ks_wp == it[0].p->dev.ks_wp && (!d.ks_wp || a.tw), "k_mfma_ks_group: entries of different position forms");
+        e.tW = (const uint8_t *)a.tw;
         args.begin[i] = wg;
         // each entry starts on a multiple of 8 workgroups (idle ones in between exit at once), so
         // its entry-relative block numbers share XCDs as the global ones do (xcd_block)
@@ -437,14 +459,16 @@ uint32_t ks_group_key(const plan_state &p, uint32_t N) {
     const bool w8 = d.waves == kKsWaves && d.ks_ap, w4 = d.waves == 4 && !d.ks_ap;
     if (!p.uploaded || !d.mfma || !d.ks || d.pad_rows || N != 32 || d.lds_N != 32 || !(w8 || w4) || d.ks_persist) return 0;
     // bf16: the grouped kernel's twins are the release instantiations (as launch_ks_k)
-    if (d.dtype == kBF16 && (d.ks_p8 || !w8)) return 0;
+    if (d.dtype == kBF16 && (d.ks_p8 || d.ks_wp || !w8)) return 0;
+    if (d.ks_wp && !w8) return 0;
 #ifndef GS_EXPERIMENTS
     // the release build instantiates the grouped kernel for 16-byte u16-position groups on 8
     // waves only: any other layout runs as single launches (which refuse it themselves)
     if (d.ks_p8 || !w8) return 0;
 #endif
-    // dtype, NT, waves, P8, RT, MAXG: fp16 and bf16 entries never share a launch
-    return (d.dtype == kBF16 ? 1u << 20 : 0u) | (d.ks_nt << 18) | (w4 ? 1u << 17 : 0u) | (d.ks_p8 ? 1u << 16 : 0u) | (d.maxr << 8) |
+    // position form, dtype, NT, waves, P8, RT, MAXG: fp16 and bf16 entries, and u16 and window
+    // positions, never share a launch
+    return (d.ks_wp ? 1u << 21 : 0u) | (d.dtype == kBF16 ? 1u << 20 : 0u) | (d.ks_nt << 18) | (w4 ? 1u << 17 : 0u) | (d.ks_p8 ? 1u << 16 : 0u) | (d.maxr << 8) |
            d.seg_cap;
 }
 

@@ -73,6 +73,7 @@ typedef struct {
     uint32_t ks_nt;               /* k_mfma_ks: A's groups by non-temporal loads (KS_NT) */
     uint32_t ks_head_groups;      /* k_mfma_ks: groups per head step (KS_HEAD; 0: every step by record) */
     uint32_t nm_tiles;            /* k_nm_mfma: 16-row tiles per workgroup (NM_TILES / the upload's rule) */
+    uint32_t ks_wpos;             /* k_mfma_ks: one-byte window positions (KS_WPOS; 0: the u16 layout) */
 } gs_plan_info;
 
 const char *gs_last_error(void);
