@@ -6,25 +6,16 @@
 #include "../hip_code/parts.hpp"
 #include "../hip_code/lds_rows.hpp"
 #include "../hip_code/merge_path.hpp"
-#include "../host/gs_plan.hpp"
+#include "../host/gather_layout.hpp"
+#include "launch_common.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 
 namespace gs {
 
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) throw gs_error(std::string(#x) + ": " + hipGetErrorString(e_), -3); \
-    } while (0)
-
 namespace {
-
-constexpr int kLdsMaxU = 12;  // 16-B staging registers per thread (k_lds_rows MAXU; device_plan.hip sizes the tiles)
 
 #ifdef GS_EXPERIMENTS
 uint64_t *g_mp_stamps = nullptr;  // set by debug_mp_timeline for one launch (diagnostic build only)
@@ -40,12 +31,6 @@ uint32_t mp_debug() {
 #endif
 }
 
-uint32_t pow2ceil(uint32_t x) {
-    uint32_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 template <class VT, int CF>
 void launch_lds(const plan_state &p, const device_arrays &a, const VT *B, VT *C, uint32_t N, hipStream_t s) {
     const device_plan &d = p.dev;
@@ -59,35 +44,14 @@ void launch_lds(const plan_state &p, const device_arrays &a, const VT *B, VT *C,
     a.t0, a.a1, a.a0, a.t1, a.t2, (const uint16_t *)a.tcol, (const VT *)a.tval, B, C, K, N, X, d.KC, d.nc, d.RSB, \
         d.rpw_max, d.seg_cap, (uint32_t)d.row_base, ksp, d.ncs, a.ws, a.t3
     auto go = [&](auto kern) {
-        // dynamic LDS above 64 KB must be opted into, once per kernel and device
-        static std::mutex mu;
-        static std::map<std::pair<int, const void *>, size_t> granted;
-        {
-            std::lock_guard<std::mutex> l(mu);
-            size_t &g = granted[{d.device, reinterpret_cast<const void *>(kern)}];
-            if (g < d.lds_bytes) {
-                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds_bytes));
-                g = d.lds_bytes;
-            }
-        }
+        grant_lds(d.device, kern, d.lds_bytes);
         hipLaunchKernelGGL(kern, grid, block, d.lds_bytes, s, GS_LDS_ARGS);
     };
     if constexpr (sizeof(VT) == 4 && CF == 4) {
         if (d.lds_dma) {  // LDS_DMA: fp32 N = 32, chunks by LDS-DMA into two buffers
             GS_CHECK(N == 32, "k_lds_rows_dma is built for N = 32");
             auto gd = [&](auto kern) {
-                static std::mutex mu;
-                static std::map<std::pair<int, const void *>, size_t> granted;
-                {
-                    std::lock_guard<std::mutex> l(mu);
-                    size_t &g = granted[{d.device, reinterpret_cast<const void *>(kern)}];
-                    if (g < d.lds_bytes) {
-                        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds_bytes));
-                        g = d.lds_bytes;
-                    }
-                }
+                grant_lds(d.device, kern, d.lds_bytes);
                 hipLaunchKernelGGL(kern, grid, block, d.lds_bytes, s, a.t0, a.a1, a.a0, a.t1, a.t2, (const uint16_t *)a.tcol,
                                    (const float *)a.tval, (const float *)B, (float *)C, K, d.KC, d.nc, d.rpw_max, d.seg_cap,
                                    (uint32_t)d.row_base, ksp, d.ncs, a.ws, a.t3);
@@ -110,7 +74,7 @@ template <class VT, class CT, int CF, int SCF>
 void launch_family(const plan_state &p, const device_arrays &a, const VT *B, VT *C, uint32_t N, hipStream_t s) {
     const device_plan &d = p.dev;
     const kernel_spec &sp = p.cg->get_kernel_spec();
-    const uint32_t X = std::min<uint32_t>(64u, pow2ceil((N + CF - 1) / CF));
+    const uint32_t X = lanes_per_row(N, (uint32_t)sizeof(VT));  // CF: dispatch_vt takes 16 B when N allows
     const uint32_t tiles = (N + X * CF - 1) / (X * CF);
     const uint32_t row_base = (uint32_t)d.row_base;
     const CT *col = (const CT *)a.col;

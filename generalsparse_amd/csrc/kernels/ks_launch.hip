@@ -8,19 +8,11 @@
 #ifdef GS_EXPERIMENTS
 #include "../hip_code/mfma_bm_exp.hpp"
 #endif
-#include "../host/gs_plan.hpp"
+#include "launch_common.hpp"
 
 #include <cstring>
-#include <map>
-#include <mutex>
 
 namespace gs {
-
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) throw gs_error(std::string(#x) + ": " + hipGetErrorString(e_), -3); \
-    } while (0)
 
 namespace {
 
@@ -29,20 +21,6 @@ namespace {
 uint32_t ks_prio_arg() {
     const config_t c = get_config();
     return (uint32_t)(c.KS_PRIO & 3) | (c.KS_FORCE_TIMEOUT ? 16u : 0u);
-}
-
-template <class KERN>
-void grant_lds(int device, KERN kern, size_t bytes) {
-    // dynamic LDS above 64 KB is opted into once per kernel and device
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, size_t> granted;
-    std::lock_guard<std::mutex> l(mu);
-    size_t &g = granted[{device, reinterpret_cast<const void *>(kern)}];
-    if (g < bytes) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)bytes));
-        g = bytes;
-    }
 }
 
 // ET: the plan's 16-bit element type (gsk::f16, or gsk::bf16 for GS_BF16 plans).  The bf16 twins are

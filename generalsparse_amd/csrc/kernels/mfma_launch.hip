@@ -6,19 +6,11 @@
 #ifdef GS_EXPERIMENTS
 #include "../hip_code/nm_mfma_exp.hpp"
 #endif
-#include "../host/gs_plan.hpp"
+#include "launch_common.hpp"
 
 #include <cstdlib>
-#include <map>
-#include <mutex>
 
 namespace gs {
-
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) throw gs_error(std::string(#x) + ": " + hipGetErrorString(e_), -3); \
-    } while (0)
 
 namespace {
 
@@ -54,17 +46,7 @@ void launch_mfma_k(const plan_state &p, const device_arrays &a, const gsk::f16 *
         if (gl == 2 && wct == 6 && mdbg == 15) kern = gsk::k_mfma_rows<CT, RT, LGKC, MAXA, false, 2, 3, 6, 15>;
     }
 #endif
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, size_t> granted;
-    {
-        std::lock_guard<std::mutex> l(mu);
-        size_t &g = granted[{d.device, reinterpret_cast<const void *>(kern)}];
-        if (g < d.lds_bytes) {
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)d.lds_bytes));
-            g = d.lds_bytes;
-        }
-    }
+    grant_lds(d.device, kern, d.lds_bytes);
     hipLaunchKernelGGL(kern, dim3((uint32_t)d.n_rows_aux * d.ksplit), dim3(kMfmaThreads), d.lds_bytes, s, a.t0,
                        a.t1, (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, B, C, (uint32_t)p.K, N, d.nc,
                        d.rpw_max, (uint32_t)d.row_base, d.ksplit, d.ncs, a.ws, a.t2, (uint64_t *)nullptr,
@@ -126,8 +108,7 @@ void debug_mfma_timeline(const plan_state &p, const void *B, void *C, uint32_t N
     auto kern = d.maxr == 2 ? (d.RSB == 9 ? timeline_kernel<2, 9>(two) : timeline_kernel<2, 8>(two))
                             : (d.RSB == 9 ? timeline_kernel<3, 9>(two) : timeline_kernel<3, 8>(two));
     const size_t lds = d.lds_bytes;
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
+    grant_lds(d.device, kern, lds);
     uint64_t *dst = nullptr;
     const size_t n = (size_t)d.n_rows_aux * d.ksplit * 64;
     HIP_OK(hipMalloc(&dst, n * 8));
@@ -165,33 +146,13 @@ void launch_nm_ctt(const plan_state &p, const device_arrays &a, const void *B, v
     auto kern = d.nm_nt ? gsk::k_nm_mfma<CT, 0, NG, true, TT> : gsk::k_nm_mfma<CT, 0, NG, false, TT>;
 #endif
     const size_t lds = (size_t)2 * gsk::kNmKC * 32 * CT + (dbg == 4 ? 4096 : 0);
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, bool> granted;
-    {
-        std::lock_guard<std::mutex> l(mu);
-        bool &g = granted[{d.device, reinterpret_cast<const void *>(kern)}];
-        if (!g) {
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds));
-            g = true;
-        }
-    }
+    grant_lds(d.device, kern, lds);
 #ifdef GS_EXPERIMENTS
     if (d.nm_ks) {
         GS_CHECK(d.nm_tiles == 8, "k_nm_mfma_ks reads the 64-row-group layout");
         auto kk = gsk::k_nm_mfma_ks<CT>;
         const size_t lds2 = (size_t)2 * gsk::kNmKC * 32 * CT;
-        static std::mutex mu2;
-        static std::map<std::pair<int, const void *>, bool> granted2;
-        {
-            std::lock_guard<std::mutex> l(mu2);
-            bool &g = granted2[{d.device, reinterpret_cast<const void *>(kk)}];
-            if (!g) {
-                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds2));
-                g = true;
-            }
-        }
+        grant_lds(d.device, kk, lds2);
         const uint32_t nb = (uint32_t)((d.n_rows_aux + 255) / 256);
         hipLaunchKernelGGL(kk, dim3(nb * d.ksplit), dim3(256), lds2, s, (const unsigned char *)a.tcol, (const gsk::f16 *)B,
                            (gsk::f16 *)C, (uint32_t)p.K, d.KC, (uint32_t)d.n_rows_aux, (uint32_t)d.row_base, d.ksplit,
@@ -217,17 +178,7 @@ void launch_nm4(const plan_state &p, const device_arrays &a, const void *B, void
     const device_plan &d = p.dev;
     auto kern = gsk::k_nm_mfma4<CT>;
     const size_t lds = gsk::nm4_lds_bytes(CT);
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, bool> granted;
-    {
-        std::lock_guard<std::mutex> l(mu);
-        bool &g = granted[{d.device, reinterpret_cast<const void *>(kern)}];
-        if (!g) {
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds));
-            g = true;
-        }
-    }
+    grant_lds(d.device, kern, lds);
     const uint32_t nb = (uint32_t)((d.n_rows_aux + 255) / 256), nch = d.KC / 4;
     GS_CHECK(p.K % gsk::kNmKC == 0 && d.ksplit >= 1 && d.ncs >= 1 && (d.ksplit - 1) * d.ncs < nch &&
                  (d.ksplit == 1 || (a.ws && a.t2)),
