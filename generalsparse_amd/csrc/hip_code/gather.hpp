@@ -89,14 +89,33 @@ __global__ __launch_bounds__(256) void k_thread_total(const uint32_t *__restrict
 // workgroup g owns BMWs [bmw_of_bmtb[g], bmw_of_bmtb[g+1]) and its waves stride
 // over them (keeps a BMTB's rows on one CU / XCD).
 // ---------------------------------------------------------------------------
-template <class VT, class CT, int CF, int SCF>
+// a gathered B piece, all zero bits unless `keep`: an entry outside its row (the aligned over-read,
+// a padding chunk) is masked in its B operand as well as in its value, so that a non-finite B
+// value of a column the row does not hold never reaches the row (0 x Inf = NaN)
+template <class RB>
+__device__ __forceinline__ RB kept_piece(RB r, bool keep) {
+    if constexpr (sizeof(RB) < 4) {
+        return keep ? r : (RB)0;
+    } else {
+        uint32_t w[sizeof(RB) / 4];
+        __builtin_memcpy(w, &r, sizeof(RB));
+        const uint32_t m = keep ? 0xffffffffu : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < sizeof(RB) / 4; k++) w[k] &= m;
+        __builtin_memcpy(&r, w, sizeof(RB));
+        return r;
+    }
+}
+
+template <class VT, class CT, int CF, int SCF, bool KEEP = true>
 __device__ __forceinline__ void wave_row(const uint32_t b, const uint32_t e, const CT *__restrict__ col,
                                          const VT *__restrict__ val, const VT *__restrict__ B, uint32_t N,
                                          uint32_t c0, uint32_t slot, uint32_t S, float (&acc)[CF]) {
     // Slot-owned SCF-entry chunks, SCF-aligned so cols and vals come in one
     // 16-byte load each; entries outside [b, e) (aligned over-read into the
     // neighbouring rows / zero padding, always valid column indices) are
-    // masked by zeroing their value, never by a branch, so all SCF B-row
+    // masked by zeroing their value and their B piece (kept_piece; KEEP = false,
+    // k_warp_rows_mc: the value only), never by a branch, so all SCF B-row
     // gathers of a chunk are in flight together.  The next chunk's A loads are
     // issued before this chunk's gathers (software pipelining).
     typedef typename raw_vec<CF * sizeof(VT)>::t RB;
@@ -126,7 +145,12 @@ __device__ __forceinline__ void wave_row(const uint32_t b, const uint32_t e, con
             const uint32_t p = p0 + j;
             const float v = (p >= b && p < e) ? (float)vv[j] : 0.f;
             VT bt[CF];
-            __builtin_memcpy(bt, &braw[j], sizeof(RB));
+            if constexpr (KEEP) {
+                const RB bk = kept_piece(braw[j], p >= b && p < e);
+                __builtin_memcpy(bt, &bk, sizeof(RB));
+            } else {
+                __builtin_memcpy(bt, &braw[j], sizeof(RB));
+            }
 #pragma unroll
             for (int k = 0; k < CF; k++) acc[k] = __builtin_fmaf(v, (float)bt[k], acc[k]);
         }
@@ -198,7 +222,14 @@ __device__ __forceinline__ void warp_rows_body(const uint32_t *__restrict__ bmw_
                     for (int j = 0; j < SCF; j++) {
                         const float v = (q + j >= b && q + j < e) ? (float)vv[j] : 0.f;
                         VT bt[CF];
-                        __builtin_memcpy(bt, &braw[j], sizeof(RB));
+                        // (k_warp_rows_mc, MC > 1, masks the value only: the selects on the B piece
+                        // cost C1 3.9%, DESIGN.md section 3 "Non-finite B on the gather families")
+                        if constexpr (MC == 1) {
+                            const RB bk = kept_piece(braw[j], q + j >= b && q + j < e);
+                            __builtin_memcpy(bt, &bk, sizeof(RB));
+                        } else {
+                            __builtin_memcpy(bt, &braw[j], sizeof(RB));
+                        }
 #pragma unroll
                         for (int k = 0; k < CF; k++) acc[k] = __builtin_fmaf(v, (float)bt[k], acc[k]);
                     }
@@ -285,7 +316,7 @@ __device__ __forceinline__ void warp_rows_body(const uint32_t *__restrict__ bmw_
                 float acc[CF];
 #pragma unroll
                 for (int k = 0; k < CF; k++) acc[k] = 0.f;
-                if (live) wave_row<VT, CT, CF, SCF>(row_ptr[r], row_ptr[r + 1], col, val, B, N, c0, slot, S, acc);
+                if (live) wave_row<VT, CT, CF, SCF, MC == 1>(row_ptr[r], row_ptr[r + 1], col, val, B, N, c0, slot, S, acc);
                 for (uint32_t off = X; off < X * S; off <<= 1) {
 #pragma unroll
                     for (int k = 0; k < CF; k++) acc[k] += __shfl_xor(acc[k], (int)off, 64);

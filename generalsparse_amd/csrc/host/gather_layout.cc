@@ -136,7 +136,10 @@ bool build_lds_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uin
                     t.src.push_back((uint32_t)e);
                 }
                 cur[i] = e;
-                while ((t.tcol.size() - base) % 4) { t.tcol.push_back(0); t.src.push_back(~0u); }
+                // padding entries (value 0) repeat the row's last column of this chunk, never a column
+                // the row does not hold: 0 x a non-finite B value must not reach another row's result
+                // (a row with no entry in the chunk ends on a multiple of 4 and gets no padding)
+                while ((t.tcol.size() - base) % 4) { t.tcol.push_back(t.tcol.back()); t.src.push_back(~0u); }
                 if (rowslot) {
                     // slot s reads entry 4i + q of its row in the q-th read of iteration i: slots
                     // {0,1,4,5} take column parity k & 1 at entry k, slots {2,3,6,7} the opposite

@@ -34,7 +34,7 @@ inline uint64_t merge_path_target(uint32_t N, uint32_t ebytes) {
 // ------------------------------------------------------------------ LDS tiles
 // Chunk-major A layout for k_lds_rows (lds_rows.hpp): for BMTB g and column
 // chunk j = [j*KC, (j+1)*KC), the entries of g's rows whose columns fall in the
-// chunk, row after row, each row padded to 4 entries (column 0, value 0) and
+// chunk, row after row, each row padded to 4 entries (its last column of the chunk, value 0) and
 // the segment padded to 8 entries so it stages as whole 16-B units.
 struct lds_tiles {
     uint32_t KC = 0, nc = 0, RSB = 0, rpw_max = 0, seg_cap = 0, waves = 0, maxr = 0;
