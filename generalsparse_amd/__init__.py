@@ -128,18 +128,99 @@ def _check_operands(info, B, C, N=None):
     return want, N
 
 
+ACTIVATIONS = {None: 0, "relu": 1}  # gs_epilogue.activation (GS_ACT_NONE / GS_ACT_RELU)
+_EPILOGUE_KEYS = ("alpha", "bias", "activation", "residual")
+
+
+def _check_activation(activation):
+    """the activation's code; checked before anything touches a device"""
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be None or 'relu', not {activation!r}")
+    return ACTIVATIONS[activation]
+
+
+def _extent(t):
+    """[first byte, one past the last byte) of a contiguous tensor or of (pointer, bytes)"""
+    if isinstance(t, tuple):
+        return t[0], t[0] + t[1]
+    return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+
+
+def _epilogue(info, device, C, N, alpha=1.0, bias=None, activation=None, residual=None):
+    """the gs_epilogue of one SpMM, or None for the identity (alpha 1, nothing else).  Everything is
+    checked here, before any launch: the activation's name first, then alpha (finite), bias (a
+    contiguous float32 GPU tensor of `rows` elements on `device`) and residual (a contiguous GPU
+    tensor of C's dtype and shape on `device` whose memory does not overlap C's).  C: the output
+    tensor, (pointer, bytes) for a raw pointer, or None when spmm allocates it."""
+    act = _check_activation(activation)
+    alpha = float(alpha)
+    if not np.isfinite(alpha):
+        raise ValueError(f"alpha must be finite, not {alpha}")
+    if act == 0 and alpha == 1.0 and bias is None and residual is None:
+        return None
+    import torch
+    want, rows = _torch_dtype(info["dtype"]), info["rows"]
+    if bias is not None:
+        if not (isinstance(bias, torch.Tensor) and bias.is_cuda and bias.device == device):
+            raise ValueError(f"bias must be a GPU tensor on {device}")
+        if bias.dtype != torch.float32:
+            raise TypeError("bias must be float32")
+        if not (bias.dim() == 1 and bias.shape[0] == rows and bias.is_contiguous()):
+            raise ValueError(f"bias must be a contiguous vector of {rows} elements (one per row of C)")
+    if residual is not None:
+        if not (isinstance(residual, torch.Tensor) and residual.is_cuda and residual.device == device):
+            raise ValueError(f"residual must be a GPU tensor on {device}")
+        if residual.dtype != want:
+            raise TypeError(f"residual must be {want}")
+        if not (tuple(residual.shape) == (rows, N) and residual.is_contiguous()):
+            raise ValueError(f"residual must be a contiguous tensor of shape ({rows}, {N})")
+        if C is not None:
+            (r0, r1), (c0, c1) = _extent(residual), _extent(C)
+            if r0 < c1 and c0 < r1:
+                raise ValueError("residual may not overlap C")
+    return _lib.GsEpilogue(alpha, act, bias.data_ptr() if bias is not None else None,
+                           residual.data_ptr() if residual is not None else None)
+
+
 class Batch:
     """a fixed list of SpMMs (plan, replica, B, C) run by gs_spmm_batch: consecutive K-split
     matrix-core entries of one instantiation are one grouped launch (k_mfma_ks_group).  The
-    argument arrays are built once; run() enqueues the whole batch on a stream."""
+    argument arrays are built once; run() enqueues the whole batch on a stream.
+    epilogues: per entry None or a dict with any of alpha / bias / activation / residual (as
+    Plan.spmm's keywords); the launches are the same with or without them (gs_spmm_batch_ex)."""
 
-    def __init__(self, entries, N):
+    def __init__(self, entries, N, epilogues=None):
         self._L = _lib.load()
         n = len(entries)
         self.plans = [e[0] for e in entries]  # keeps the plans alive
+        if epilogues is not None:
+            if len(epilogues) != n:
+                raise ValueError("epilogues must hold one item (None or a dict) per entry")
+            for ep in epilogues:
+                if ep is not None:
+                    unknown = set(ep) - set(_EPILOGUE_KEYS)
+                    if unknown:
+                        raise ValueError(f"unknown epilogue keys {sorted(unknown)}")
+                    _check_activation(ep.get("activation"))
         for e in entries:
             if not isinstance(e[2], int):
                 _check_operands(e[0].info(), e[2], None if isinstance(e[3], int) else e[3], int(N))
+        self._epi = None
+        if epilogues is not None and any(ep is not None for ep in epilogues):
+            self._keep = epilogues  # keeps the bias and residual tensors alive
+            self._eps = []
+            for e, ep in zip(entries, epilogues):
+                if ep is None:
+                    self._eps.append(None)
+                    continue
+                info = e[0].info()
+                if isinstance(e[2], int):
+                    raise ValueError("an entry with an epilogue needs B as a tensor (its device is checked)")
+                ebytes = 4 if info["dtype"] == GS_F32 else 2
+                C = (e[3], info["rows"] * int(N) * ebytes) if isinstance(e[3], int) else e[3]
+                self._eps.append(_epilogue(info, e[2].device, C, int(N), **ep))
+            self._epi = (ctypes.POINTER(_lib.GsEpilogue) * n)(
+                *[ctypes.pointer(x) if x is not None else None for x in self._eps])
         self._p = (ctypes.c_void_p * n)(*[e[0]._h for e in entries])
         self._r = (ctypes.c_int * n)(*[int(e[1]) for e in entries])
         self._b = (ctypes.c_void_p * n)(*[e[2] if isinstance(e[2], int) else e[2].data_ptr() for e in entries])
@@ -147,6 +228,10 @@ class Batch:
         self.n, self.N = n, int(N)
 
     def run(self, stream=0):
+        if self._epi is not None:
+            _lib.check(self._L.gs_spmm_batch_ex(self._p, self._r, self._b, self._c, self._epi, self.n, self.N,
+                                                ctypes.c_void_p(stream)))
+            return
         _lib.check(self._L.gs_spmm_batch(self._p, self._r, self._b, self._c, self.n, self.N, ctypes.c_void_p(stream)))
 
     def launches(self):
@@ -291,18 +376,38 @@ class Plan:
     def add_replica(self):
         _lib.check(self._L.gs_plan_add_replica(self._h))
 
-    def spmm(self, B, C=None, replica=0, stream=None):
+    def spmm(self, B, C=None, replica=0, stream=None, *, alpha=1.0, bias=None, activation=None, residual=None):
         """C = A @ B on the GPU.  B: (K, N) torch tensor on the plan's device, in
-        the plan's dtype.  Enqueued on torch's current stream."""
+        the plan's dtype.  Enqueued on torch's current stream.
+        The keywords add an element-wise epilogue (gs_spmm_ex), in this order on the fp32 sums:
+        times alpha, plus bias[row] (float32, one per row of C), activation ("relu"), plus residual
+        (C's dtype and shape, no overlap with C); C is rounded once.  epilogue_fused(N) tells whether
+        the plan applies it inside its kernel or as a pass over C.  Every argument is checked before
+        anything is launched, so a refused call leaves C untouched."""
+        _check_activation(activation)
         import torch
         info = self.info()
         want, N = _check_operands(info, B, C)
+        epi = _epilogue(info, B.device, C, N, alpha, bias, activation, residual)
         if C is None:
             C = torch.empty((info["rows"], N), dtype=want, device=B.device)
         s = stream if stream is not None else torch.cuda.current_stream(B.device).cuda_stream
-        _lib.check(self._L.gs_spmm_replica(self._h, int(replica), ctypes.c_void_p(B.data_ptr()),
-                                           ctypes.c_void_p(C.data_ptr()), int(N), ctypes.c_void_p(s)))
+        if epi is None:
+            _lib.check(self._L.gs_spmm_replica(self._h, int(replica), ctypes.c_void_p(B.data_ptr()),
+                                               ctypes.c_void_p(C.data_ptr()), int(N), ctypes.c_void_p(s)))
+        else:
+            _lib.check(self._L.gs_spmm_ex(self._h, int(replica), ctypes.c_void_p(B.data_ptr()),
+                                          ctypes.c_void_p(C.data_ptr()), int(N), ctypes.byref(epi), ctypes.c_void_p(s)))
         return C
+
+    def epilogue_fused(self, N):
+        """1 when spmm at dense width N applies an epilogue inside its kernel (k_mfma_ks at the
+        plan's tile width: one rounding), 0 when it runs as a pass over C after the kernels
+        (every other family; 16-bit plans then round twice); gs_plan_epilogue_fused"""
+        k = self._L.gs_plan_epilogue_fused(self._h, int(N))
+        if k < 0:
+            _lib.check(k)
+        return k
 
     def rotation(self, Bs, Cs):
         """the (B, C) pairs of spmm_rotate, checked and packed once; .run(count, first) enqueues"""

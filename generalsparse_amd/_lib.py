@@ -38,8 +38,20 @@ class GsPlanInfo(ctypes.Structure):
                 ("nm_tiles", ctypes.c_uint32), ("ks_wpos", ctypes.c_uint32)]
 
 
+class GsEpilogue(ctypes.Structure):
+    """gs_epilogue: alpha, activation (0 none, 1 relu), bias (fp32, one per row), residual (plan dtype)"""
+    _fields_ = [("alpha", ctypes.c_float), ("activation", ctypes.c_int), ("bias", ctypes.c_void_p),
+                ("residual", ctypes.c_void_p)]
+
+
 # every symbol include/generalsparse.h declares, with its ctypes signature
 SIGNATURES = {
+    "gs_spmm_ex": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                    ctypes.POINTER(GsEpilogue), ctypes.c_void_p], ctypes.c_int),
+    "gs_spmm_batch_ex": ([ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
+                          ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.POINTER(GsEpilogue)), ctypes.c_int,
+                          ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "gs_plan_epilogue_fused": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "gs_plan_logical_check": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int], ctypes.c_int),
     "gs_plan_array_set_u64": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
     "gs_last_error": ([], ctypes.c_char_p),

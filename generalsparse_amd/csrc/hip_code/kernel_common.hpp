@@ -1,5 +1,5 @@
 // hip_code/kernel_common.hpp -- what the kernel family headers share: the raw vector types,
-// the fp32 load / store / atomic helpers, the read-once loads, xcd_block, fma_row, and the
+// the fp32 load / store / atomic helpers, the read-once loads, xcd_block, epilogue_apply, fma_row, and the
 // helpers of more than one matrix-core family (fragment types, b_piece, ks_slab_wait).
 // A family header includes this one and nothing else of hip_code/.
 #pragma once
@@ -140,6 +140,22 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
 #endif
     const uint32_t q = n >> 3, r = n & 7u, x = b & 7u;
     return (x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + (b >> 3);
+}
+
+// The epilogue of one element of C (gsk::epilogue, kernel_consts.hpp): acc = the fp32 value of
+// (A * B)[row][col]; res = float(residual[row][col]), loaded by the caller when e.residual is set
+// and ignored otherwise.  The stages in their fixed order, a stage that is not requested skipped
+// (never an added zero: -0 and NaN pass as they are); the caller rounds the result once, to the
+// plan dtype.  Called by k_mfma_ks's store_item (the fused path: acc is the kernel's fp32 sum)
+// and by k_epilogue (the post-pass: acc is float(C) as the family wrote it), so the two agree.
+__device__ __forceinline__ float epilogue_apply(const epilogue &e, float acc, size_t row, float res) {
+    // (__fmul_rn / __fadd_rn: never contracted into an fma, so every stage rounds on its own in
+    // both callers)
+    float t = __fmul_rn(e.alpha, acc);
+    if (e.bias) t = __fadd_rn(t, e.bias[row]);
+    if (e.act == kEpiRelu) t = t < 0.f ? 0.f : t;  // NaN: the comparison is false, NaN stays
+    if (e.residual) t = __fadd_rn(t, res);
+    return t;
 }
 
 // one sparse entry times a CF-wide B segment

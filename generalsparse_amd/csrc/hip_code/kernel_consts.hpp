@@ -20,8 +20,24 @@ constexpr int kMfmaWaves = 16, kMfmaCompute = 6, kMfmaBWaves = 4, kMfmaAWaves = 
 // GLDS = g > 0: g waves issue the B rows (LDS-DMA), the other 10 - g load and scatter entries
 constexpr int kMfmaBWavesG = 2, kMfmaAWavesG = 8;
 
-// k_mfma_ks_group: entries of one grouped launch (kernel arguments, ~3.2 KB of the 4 KB)
+// k_mfma_ks_group: entries of one grouped launch (kernel arguments, ~3.9 KB of the 4 KB)
 constexpr int kKsGroupMax = 32;
+
+// The element-wise epilogue of one SpMM (gs_epilogue of include/generalsparse.h, the same 24 bytes;
+// the stages and their order: epilogue_apply, kernel_common.hpp).  A kernel argument of k_mfma_ks,
+// a part of k_mfma_ks_group's entries and the argument of the post-pass k_epilogue (parts.hpp).
+enum : int32_t { kEpiNone = 0, kEpiRelu = 1 };
+struct epilogue {
+    float alpha;           // 1: no scaling
+    int32_t act;           // kEpiNone / kEpiRelu
+    const float *bias;     // one fp32 per row of C, or null
+    const void *residual;  // rows x N of the plan dtype, or null
+};
+static_assert(sizeof(epilogue) == 24, "epilogue is 24 bytes (ks_entry, gs_epilogue)");
+GSK_HD constexpr epilogue epilogue_identity() { return epilogue{1.f, kEpiNone, nullptr, nullptr}; }
+GSK_HD constexpr bool epilogue_is_identity(const epilogue &e) {
+    return e.alpha == 1.f && e.act == kEpiNone && !e.bias && !e.residual;
+}
 
 // k_mfma_ks: wave image row stride (conflict-free ds_read_b128 fragment reads)
 constexpr uint32_t kKsStride = 96;

@@ -65,6 +65,9 @@ __device__ constexpr int vmcnt_imm() {
 // one base per group and two VALU per entry, kept for the clearing pass
 // ET (f16 or bf16, GS_BF16 plans): the element type of A's values, B and C.  The kernel moves
 // 16-bit words whatever they hold; ET selects the MFMA (mfma_elem) and the store conversion only
+// epi (gs_spmm_ex's epilogue, kernel_consts.hpp): store_item applies epilogue_apply to the fp32 sum --
+// after the wave reduction at S == 1, after the last ticket holder's slab combine otherwise -- and
+// rounds once; the identity (the default: emitted programs, k_mfma_ks_persist) stores as before
 // GS_KS_FULL_TILE (1; 0 in a variant build for the A/B): the step loop's fast iterations, see ks_body
 #ifndef GS_KS_FULL_TILE
 #define GS_KS_FULL_TILE 1
@@ -76,7 +79,8 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
                                         const ET *__restrict__ B, ET *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
                                         uint32_t NS, uint32_t nwg, uint32_t row_base, float *__restrict__ slabs,
                                         uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps, uint32_t bx,
-                                        uint32_t prio, const uint8_t *__restrict__ tW = nullptr) {
+                                        uint32_t prio, const uint8_t *__restrict__ tW = nullptr,
+                                        const epilogue &epi = epilogue_identity()) {
     constexpr bool P8 = PF == kKsPos8, WP = PF == kKsPosWin;
     constexpr uint32_t RB = 32 * CT;  // bytes per LDS B row (a 16*CT-column tile)
     constexpr uint32_t UB = 2 * CT;   // 16-B units per B row
@@ -388,10 +392,23 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
         for (uint32_t w = 1; w < WR; w++) sum += red[w * NI + t];
         return sum;
     };
+    // a launch with an epilogue (kernel arguments: a wave-uniform branch, after the step loop and
+    // the K-range combine; the identity takes the plain stores)
+    const bool fused = !epilogue_is_identity(epi);
     auto store_item = [&](uint32_t t, const f4v &v) {
         const uint32_t ln = t & 63u, tt = t >> 6, rt = tt / CT, ct = tt % CT;
         const uint32_t col = 16u * ct + (ln & 15u), rb = 16u * rt + 4u * (ln >> 4);
         if (col >= nv) return;
+        if (fused) {  // the launch's epilogue on the fp32 sum, rounded once (epilogue_apply)
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++)
+                if (rb + i < R) {
+                    const size_t row = (size_t)(row_base + r0 + rb + i), at = row * N + col0 + col;
+                    const float res = epi.residual ? (float)static_cast<const ET *>(epi.residual)[at] : 0.f;
+                    C[at] = (ET)epilogue_apply(epi, v[i], row, res);
+                }
+            return;
+        }
 #pragma unroll
         for (uint32_t i = 0; i < 4; i++)
             if (rb + i < R) C[(size_t)(row_base + r0 + rb + i) * N + col0 + col] = (ET)v[i];
@@ -469,10 +486,11 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks(const uint32_t *__restrict__
                                                     uint32_t row_base, float *__restrict__ slabs,
                                                     uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps = nullptr,
                                                     uint32_t prio = 0,
-                                                    const uint8_t *__restrict__ tW = nullptr) {  // kKsPosWin: window byte per group
+                                                    const uint8_t *__restrict__ tW = nullptr,  // kKsPosWin: window byte per group
+                                                    epilogue epi = epilogue_identity()) {  // applied in store_item
     // nwg == gridDim.x (an argument: kernarg preload)
     ks_body<CT, RT, W, D, MAXG, STAMPS, AP, PF, NTL, ET>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nwg, row_base, slabs,
-                                                    arrivals, stamps, blockIdx.x, prio, tW);
+                                                    arrivals, stamps, blockIdx.x, prio, tW, epi);
 }
 
 #ifdef GS_EXPERIMENTS
@@ -533,7 +551,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_persist(const uint32_t *__re
 // entries are kernel arguments (ks_group_args, read through the kernarg segment with scalar
 // loads); every entry has its own plan replica (distinct K-range tickets and slabs).
 // ---------------------------------------------------------------------------
-struct ks_entry {  // 96 B
+struct ks_entry {  // 120 B
     const uint32_t *tbr;
     const u32x4 *tP, *tV;
     const u32x2 *steps;
@@ -543,14 +561,16 @@ struct ks_entry {  // 96 B
     uint32_t *arrivals;
     uint32_t K, S, NS, nwg, row_base, pad0;  // pad0: the entry's head-step group count
     const uint8_t *tW;  // kKsPosWin: window byte per group
+    epilogue epi;       // the entry's epilogue (the identity: plain stores)
 };
-static_assert(sizeof(ks_entry) == 96, "ks_entry is 96 bytes");
+static_assert(sizeof(ks_entry) == 120, "ks_entry is 120 bytes");
 // kKsGroupMax: kernel_consts.hpp
 struct ks_group_args {
     uint32_t begin[kKsGroupMax + 1];  // first workgroup of each entry (+ the total)
     uint32_t n, N, pad[2];  // pad[0]: k_mfma_ks's prio
     ks_entry e[kKsGroupMax];
 };
+static_assert(sizeof(ks_group_args) <= 4096, "ks_group_args must fit the 4 KB kernarg segment");
 
 template <int CT, int RT, int W, int D, int MAXG, int PF = kKsPosU16, bool AP = true, int NTL = 0, class ET = f16>
 __global__ __launch_bounds__(64 * W) void k_mfma_ks_group(ks_group_args args) {
@@ -564,7 +584,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_group(ks_group_args args) {
     if (bx - args.begin[sel] >= e.nwg) return;  // padding up to the next entry's multiple of 8
     ks_body<CT, RT, W, D, MAXG, false, AP, PF, NTL, ET>(e.tbr, e.tP, e.tV, e.steps, (const ET *)e.B, (ET *)e.C, e.K, args.N, e.S, e.NS,
                                                    e.nwg, e.row_base, e.slabs, e.arrivals, nullptr, bx - args.begin[sel],
-                                                   args.pad[0] | (e.pad0 << 8), e.tW);
+                                                   args.pad[0] | (e.pad0 << 8), e.tW, e.epi);
 }
 
 }  // namespace gsk

@@ -1,6 +1,7 @@
 // hip_code/parts.hpp -- the element-wise companions of the other families: k_combine_parts
-// (parent-indexed sub-matrices), k_add_parts (MP_COL_PARTS) and k_finalize_rows (fp32 workspace
-// rows).  Instantiated by kernels/device_plan.hip and kernels/gather_launch.hip.
+// (parent-indexed sub-matrices), k_add_parts (MP_COL_PARTS), k_finalize_rows (fp32 workspace
+// rows) and k_epilogue (the epilogue as a post-pass).  Instantiated by kernels/device_plan.hip
+// and kernels/gather_launch.hip.
 #pragma once
 
 #include "kernel_common.hpp"
@@ -49,6 +50,33 @@ __global__ __launch_bounds__(256) void k_finalize_rows(const uint32_t *__restric
         C[idx] = (VT)ws[idx];
         ws[idx] = 0.f;
     }
+}
+
+// The epilogue as a post-pass, in place on C (total = rows x N elements): what every launch that
+// k_mfma_ks does not fuse runs after its last kernel.  acc = float(C) as the family wrote it, so a
+// 16-bit plan rounds twice (an fp32 plan gives the fused path's bits).  Grid-stride; vec: 16-byte
+// accesses (N * sizeof(VT) a multiple of 16 and C, the residual 16-byte aligned: a piece never
+// crosses a row), else one element per item.  Row e / N selects the bias.
+template <class VT>
+__global__ __launch_bounds__(256) void k_epilogue(VT *__restrict__ C, epilogue epi, uint64_t total, uint32_t N,
+                                                  uint32_t vec) {
+    constexpr int CF = 16 / (int)sizeof(VT);
+    const uint64_t first = (uint64_t)blockIdx.x * 256 + threadIdx.x, stride = (uint64_t)gridDim.x * 256;
+    const VT *__restrict__ res = static_cast<const VT *>(epi.residual);
+    if (vec) {
+        for (uint64_t v = first; v < total / CF; v += stride) {
+            const uint64_t e = v * CF, row = e / N;
+            float x[CF], r[CF] = {};
+            load_f32<VT, CF>(C + e, x);
+            if (res) load_f32<VT, CF>(res + e, r);
+#pragma unroll
+            for (int k = 0; k < CF; k++) x[k] = epilogue_apply(epi, x[k], row, r[k]);
+            store_f32<VT, CF>(C + e, x);
+        }
+        return;
+    }
+    for (uint64_t e = first; e < total; e += stride)
+        C[e] = (VT)epilogue_apply(epi, (float)C[e], e / N, res ? (float)res[e] : 0.f);
 }
 
 }  // namespace gsk

@@ -4,6 +4,7 @@
 #include "index_compress.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -163,9 +164,14 @@ replica_scratch &ensure_scratch(parent_group &g, int replica, uint32_t N, size_t
 // multi-kernel executor: zero the output rows of empty row intervals, then run each
 // sub-matrix's kernel on the same stream (each writes only its own rows); parent-indexed
 // sub-matrices run into their scratch outputs, summed into C per divided range
-void spmm_all(gs_plan *p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream) {
+// epi (null: none, the launches of before): applied inside k_mfma_ks where gs::epilogue_fuses
+// admits the plan, else by the post-pass k_epilogue after the last launch
+void spmm_all(gs_plan *p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream,
+              const gsk::epilogue *epi = nullptr) {
     if (!divided(p)) {
-        gs::launch_spmm(p->st, replica, B, C, N, stream);
+        const bool fuse = epi && gs::epilogue_fuses(p->st, N);
+        gs::launch_spmm(p->st, replica, B, C, N, stream, fuse ? epi : nullptr);
+        if (epi && !fuse) gs::launch_epilogue(C, p->st.M, N, p->st.dev.dtype, *epi, stream);
         return;
     }
     auto ks = kernel_states(p);
@@ -184,6 +190,19 @@ void spmm_all(gs_plan *p, int replica, const void *B, void *C, uint32_t N, hipSt
         }
         gs::combine_parts(r.ptrs_dev, g.rows_dev, (uint32_t)g.subs.size(), C, g.base, g.rows, N, dtype, stream);
     }
+    if (epi) gs::launch_epilogue(C, p->st.M, N, dtype, *epi, stream);
+}
+
+// a caller's gs_epilogue, checked: false for NULL or the identity (the plain launches), else *out
+// is the kernels' form.  Refused (GS_ERR) before any launch: an unknown activation, a non-finite
+// alpha, the residual being C
+bool checked_epilogue(const gs_epilogue *e, const void *C, gsk::epilogue *out) {
+    if (!e) return false;
+    GS_CHECK(e->activation == GS_ACT_NONE || e->activation == GS_ACT_RELU, "gs_epilogue: unknown activation");
+    GS_CHECK(std::isfinite(e->alpha), "gs_epilogue: alpha must be finite");
+    GS_CHECK(!e->residual || e->residual != C, "gs_epilogue: the residual may not be C");
+    *out = gsk::epilogue{e->alpha, e->activation == GS_ACT_RELU ? gsk::kEpiRelu : gsk::kEpiNone, e->bias, e->residual};
+    return !gsk::epilogue_is_identity(*out);
 }
 
 }  // namespace
@@ -764,10 +783,26 @@ int gs_plan_add_replica(gs_plan_t *p) {
 }
 
 int gs_spmm_replica(gs_plan_t *p, int replica, const void *B, void *C, int N, gs_stream_t stream) {
+    return gs_spmm_ex(p, replica, B, C, N, nullptr, stream);
+}
+
+int gs_spmm_ex(gs_plan_t *p, int replica, const void *B, void *C, int N, const gs_epilogue *epi, gs_stream_t stream) {
     return guard([&] {
         GS_CHECK(p && B && C && N > 0, "bad argument");
-        spmm_all(p, replica, B, C, (uint32_t)N, (hipStream_t)stream);
+        gsk::epilogue e;
+        const bool on = checked_epilogue(epi, C, &e);
+        spmm_all(p, replica, B, C, (uint32_t)N, (hipStream_t)stream, on ? &e : nullptr);
     });
+}
+
+int gs_plan_epilogue_fused(gs_plan_t *p, int N) {
+    int fused = 0;
+    const int rc = guard([&] {
+        GS_CHECK(p && N > 0, "bad argument");
+        GS_CHECK(divided(p) || p->st.uploaded, "plan is not on the device");
+        fused = !divided(p) && gs::epilogue_fuses(p->st, (uint32_t)N) ? 1 : 0;
+    });
+    return rc < 0 ? rc : fused;
 }
 
 int gs_spmm_rotate(gs_plan_t *p, int count, int first, const void *const *B_ptrs, void *const *C_ptrs, int n_ptrs,
@@ -812,22 +847,44 @@ std::vector<batch_launch> plan_batch(gs_plan_t *const *plans, const int *replica
 
 int gs_spmm_batch(gs_plan_t *const *plans, const int *replicas, const void *const *B, void *const *C, int n, int N,
                   gs_stream_t stream) {
+    return gs_spmm_batch_ex(plans, replicas, B, C, nullptr, n, N, stream);
+}
+
+int gs_spmm_batch_ex(gs_plan_t *const *plans, const int *replicas, const void *const *B, void *const *C,
+                     const gs_epilogue *const *epi, int n, int N, gs_stream_t stream) {
     return guard([&] {
         GS_CHECK(plans && replicas && B && C && n >= 0 && N > 0, "bad argument");
         hipStream_t s = (hipStream_t)stream;
         for (int i = 0; i < n; i++) GS_CHECK(B[i] && C[i], "bad batch entry " + std::to_string(i));
+        // every entry's epilogue is checked before the first launch
+        std::vector<gsk::epilogue> ep((size_t)n, gsk::epilogue_identity());
+        std::vector<char> on((size_t)n, 0);
+        for (int i = 0; epi && i < n; i++) on[(size_t)i] = checked_epilogue(epi[i], C[i], &ep[(size_t)i]);
+        // (the grouping is plan_batch's: an epilogue never splits a group)
         for (const batch_launch &l : plan_batch(plans, replicas, n, N)) {
-            if (l.idx.size() == 1) {
+            if (l.idx.size() == 1 && l.key == 0) {
                 const int i = l.idx[0];
-                if (l.key == 0)
-                    spmm_all(plans[i], replicas[i], B[i], C[i], (uint32_t)N, s);
-                else
-                    gs::launch_spmm(plans[i]->st, replicas[i], B[i], C[i], (uint32_t)N, s);
+                spmm_all(plans[i], replicas[i], B[i], C[i], (uint32_t)N, s, on[(size_t)i] ? &ep[(size_t)i] : nullptr);
                 continue;
             }
-            std::vector<gs::ks_group_item> grp;
-            for (int i : l.idx) grp.push_back({&plans[i]->st, replicas[i], B[i], C[i]});
-            gs::launch_ks_group(grp, (uint32_t)N, s);
+            // k_mfma_ks entries (key != 0: undivided plans at their tile width, no scratch output): the
+            // epilogue in the kernel, or with EPILOGUE_FUSE = 0 the post-pass after the launch
+            bool any = false;
+            for (int i : l.idx) any |= on[(size_t)i] != 0;
+            const bool fuse = any && gs::epilogue_fuses(plans[l.idx[0]]->st, (uint32_t)N);
+            if (l.idx.size() == 1) {
+                const int i = l.idx[0];
+                gs::launch_spmm(plans[i]->st, replicas[i], B[i], C[i], (uint32_t)N, s, fuse ? &ep[(size_t)i] : nullptr);
+            } else {
+                std::vector<gs::ks_group_item> grp;
+                for (int i : l.idx)
+                    grp.push_back({&plans[i]->st, replicas[i], B[i], C[i], fuse ? ep[(size_t)i] : gsk::epilogue_identity()});
+                gs::launch_ks_group(grp, (uint32_t)N, s);
+            }
+            if (any && !fuse)
+                for (int i : l.idx)
+                    if (on[(size_t)i])
+                        gs::launch_epilogue(C[i], plans[i]->st.M, (uint32_t)N, plans[i]->st.dev.dtype, ep[(size_t)i], s);
         }
     });
 }

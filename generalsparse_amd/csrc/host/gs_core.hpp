@@ -123,6 +123,8 @@ struct config_t {
     int64_t KS_WPOS = 0;         // k_mfma_ks, fp16 at N = 32: one-byte entry positions inside 5-row windows of the wave
                                  // image + one window byte per group (25 B per group of 8 instead of 32; every
                                  // group lies in one window).  Other shapes keep the u16 layout
+    int64_t EPILOGUE_FUSE = 1;   // an epilogue (gs_spmm_ex) of a k_mfma_ks plan at its tile width: 1 in the kernel's
+                                 // store (one rounding), 0 the post-pass k_epilogue every other family takes (the A/B)
     int64_t KS_HEAD = 1;        // k_mfma_ks: the head steps (each wave's first kKsDepth k-steps) at fixed, padded
                                  // places, loaded without their records (when the padding costs <= 6% more groups)
     int64_t KS_PERSIST = 0;      // k_mfma_ks: persistent grid size pulling (row block, K range) units (experiments build)

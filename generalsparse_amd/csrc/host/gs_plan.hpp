@@ -4,6 +4,7 @@
 #include "operator.hpp"
 #include "device_layout.hpp"
 #include "../hip_code/idx_formula.hpp"
+#include "../hip_code/kernel_consts.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -145,7 +146,15 @@ void memset_rows(void *C, uint64_t lo, uint64_t hi, uint32_t N, size_t e, hipStr
 // sub-matrices' scratch outputs; parts / rows are device arrays of n entries)
 void combine_parts(const void *const *parts, const uint32_t *rows, uint32_t n, void *C, uint64_t row0, uint64_t P,
                    uint32_t N, int dtype, hipStream_t stream);
-void launch_spmm(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream);
+// epi (null: none): the launch's epilogue, applied inside k_mfma_ks -- only for a plan and width
+// that epilogue_fuses admits; every other launch takes the post-pass launch_epilogue after it
+void launch_spmm(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream,
+                 const gsk::epilogue *epi = nullptr);
+// the plan runs k_mfma_ks at its tile width N through launch_mfma, writing C itself (no pad_rows
+// scratch, static grid), and EPILOGUE_FUSE is on: launch_spmm applies an epilogue in the kernel
+bool epilogue_fuses(const plan_state &p, uint32_t N);
+// the post-pass: k_epilogue in place on C (rows x N of dtype) -- allocates nothing
+void launch_epilogue(void *C, uint64_t rows, uint32_t N, int dtype, const gsk::epilogue &epi, hipStream_t stream);
 // uploads the CSR arrays a matrix-core plan deferred (every replica), for a launch at another dense width
 void ensure_csr(plan_state &p);
 void debug_mp_timeline(const plan_state &p, const void *B, void *C, uint32_t N, hipStream_t s, uint64_t *host,
@@ -153,12 +162,15 @@ void debug_mp_timeline(const plan_state &p, const void *B, void *C, uint32_t N, 
 void debug_mfma_timeline(const plan_state &p, const void *B, void *C, uint32_t N, hipStream_t s, uint64_t *host,
                          size_t n_host);
 // mfma_launch.hip: k_mfma_rows / k_nm_mfma (and k_mfma_ks through launch_ks) at the plan's N
-void launch_mfma(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
+// (epi: k_mfma_ks plans only, epilogue_fuses)
+void launch_mfma(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+                 const gsk::epilogue &epi = gsk::epilogue_identity());
 void launch_nm(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
 // gather_launch.hip: the CUDA-core gather families and k_lds_rows
 void launch_gather(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
 // ks_launch.hip: k_mfma_ks (K-split, wave-autonomous matrix-core row blocks)
-void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
+void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+               const gsk::epilogue &epi = gsk::epilogue_identity());
 // grouped k_mfma_ks launches (gs_spmm_batch): one grid over up to 32 entries of one
 // instantiation (equal nonzero ks_group_key); every entry a distinct (plan, replica)
 struct ks_group_item {
@@ -166,6 +178,7 @@ struct ks_group_item {
     int replica;
     const void *B;
     void *C;
+    gsk::epilogue epi = gsk::epilogue_identity();  // applied in the kernel (store_item)
 };
 uint32_t ks_group_key(const plan_state &p, uint32_t N);  // 0: not groupable
 void launch_ks_group(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s);

@@ -814,7 +814,32 @@ void free_device(plan_state &p) {
     p.uploaded = false;
 }
 
-static void launch_body(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream) {
+bool epilogue_fuses(const plan_state &p, uint32_t N) {
+    const device_plan &d = p.dev;
+    return p.uploaded && d.mfma && d.ks && !d.nm && N == d.lds_N && !d.pad_rows && !d.ks_persist &&
+           get_config().EPILOGUE_FUSE != 0;
+}
+
+void launch_epilogue(void *C, uint64_t rows, uint32_t N, int dtype, const gsk::epilogue &epi, hipStream_t stream) {
+    const uint64_t total = rows * N;
+    GS_CHECK(total < (1ull << 40), "launch_epilogue: bad sizes");
+    if (total == 0 || gsk::epilogue_is_identity(epi)) return;
+    // 16-byte accesses when every row is a whole number of them and both pointers are aligned
+    const size_t e = elem_bytes(dtype);
+    const uint32_t vec = ((size_t)N * e) % 16 == 0 && (uintptr_t)C % 16 == 0 && (uintptr_t)epi.residual % 16 == 0;
+    const uint64_t items = vec ? total / (16 / e) : total;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 255) / 256, 4096);
+    if (dtype == kF32)
+        hipLaunchKernelGGL(gsk::k_epilogue<float>, dim3(blocks), dim3(256), 0, stream, (float *)C, epi, total, N, vec);
+    else if (dtype == kBF16)
+        hipLaunchKernelGGL(gsk::k_epilogue<gsk::bf16>, dim3(blocks), dim3(256), 0, stream, (gsk::bf16 *)C, epi, total, N, vec);
+    else
+        hipLaunchKernelGGL(gsk::k_epilogue<gsk::f16>, dim3(blocks), dim3(256), 0, stream, (gsk::f16 *)C, epi, total, N, vec);
+    HIP_OK(hipGetLastError());
+}
+
+static void launch_body(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream,
+                        const gsk::epilogue &epi) {
     // (the upload builds no other layout for a bf16 plan: choose_matrix_core_layout, LDS_STAGE_B)
     GS_CHECK(p.dev.dtype != kBF16 || (!p.dev.nm && !p.dev.lds && (!p.dev.mfma || p.dev.ks)),
              "bf16 plans run k_mfma_ks or a gather family: the other matrix-core and LDS kernels are fp16 / fp32 kernels");
@@ -823,9 +848,10 @@ static void launch_body(plan_state &p, int replica, const void *B, void *C, uint
         return;
     }
     if (p.dev.mfma && N == p.dev.lds_N) {
-        launch_mfma(p, p.dev.replicas[replica], B, C, N, stream);
+        launch_mfma(p, p.dev.replicas[replica], B, C, N, stream, epi);
         return;
     }
+    GS_CHECK(gsk::epilogue_is_identity(epi), "only k_mfma_ks applies an epilogue in the kernel (epilogue_fuses)");
     if (!p.dev.replicas[replica].col) {  // matrix-core plan at another dense width
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         HIP_OK(hipStreamIsCapturing(stream, &cs));
@@ -837,20 +863,24 @@ static void launch_body(plan_state &p, int replica, const void *B, void *C, uint
     launch_gather(p, p.dev.replicas[replica], B, C, N, stream);
 }
 
-void launch_spmm(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream) {
+void launch_spmm(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream,
+                 const gsk::epilogue *epi) {
     GS_CHECK(p.uploaded, "plan is not on the device");
+    const gsk::epilogue ep = epi ? *epi : gsk::epilogue_identity();
+    GS_CHECK(gsk::epilogue_is_identity(ep) || epilogue_fuses(p, N),
+             "launch_spmm: this plan and width take the epilogue as a post-pass (launch_epilogue)");
     GS_CHECK(replica >= 0 && (size_t)replica < p.dev.replicas.size(), "bad replica index");
     GS_CHECK(N >= 1, "N >= 1");
     if (p.dev.pad_rows) {
         GS_CHECK(N <= p.dev.pad_N, "row-padded plan built for N=" + std::to_string(p.dev.pad_N) +
                                        ": its scratch output holds no wider B (re-run the pipeline for this N)");
         void *scr = p.dev.replicas[replica].pad_out;
-        launch_body(p, replica, B, scr, N, stream);
+        launch_body(p, replica, B, scr, N, stream, ep);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(C, scr, (size_t)p.M * N * elem_bytes(p.dev.dtype), hipMemcpyDeviceToDevice, stream));
         return;
     }
-    launch_body(p, replica, B, C, N, stream);
+    launch_body(p, replica, B, C, N, stream, ep);
 }
 
 }  // namespace gs

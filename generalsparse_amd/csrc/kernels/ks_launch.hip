@@ -28,7 +28,7 @@ uint32_t ks_prio_arg() {
 // the experiments-build variants below stay fp16 kernels and refuse a bf16 plan
 template <int CT, int RT, int MAXG, bool STAMPS = false, int W = (int)kKsWaves, class ET = gsk::f16>
 void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s,
-                 uint64_t *stamps = nullptr) {
+                 uint64_t *stamps = nullptr, const gsk::epilogue &epi = gsk::epilogue_identity()) {
     const device_plan &d = p.dev;
     constexpr bool F16 = std::is_same<ET, gsk::f16>::value;
     if constexpr (!F16) {
@@ -43,13 +43,13 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
     // SIMD; C2 48-98 us against 14-30 us with 8 waves, profiles/r04a), experiments build only
     if constexpr (F16 && W == (int)kKsWaves && !STAMPS) {
         if (d.waves == 16) {
-            launch_ks_k<CT, RT, MAXG, false, 16>(p, a, B, C, N, s, stamps);
+            launch_ks_k<CT, RT, MAXG, false, 16>(p, a, B, C, N, s, stamps, epi);
             return;
         }
         // KS_WAVES = 12 (N = 32, RT <= 5): three waves per SIMD (r06 A/B)
         if constexpr (CT == 2 && RT <= 5) {
             if (d.waves == 12) {
-                launch_ks_k<CT, RT, MAXG, false, 12>(p, a, B, C, N, s, stamps);
+                launch_ks_k<CT, RT, MAXG, false, 12>(p, a, B, C, N, s, stamps, epi);
                 return;
             }
         }
@@ -65,7 +65,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
             hipLaunchKernelGGL(kd, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(64 * W), d.lds_bytes, s,
                                a.t0, (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C,
                                (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit, (uint32_t)d.row_base,
-                               a.ws, a.t2, stamps, ks_prio_arg(), (const uint8_t *)nullptr);
+                               a.ws, a.t2, stamps, ks_prio_arg(), (const uint8_t *)nullptr, epi);
             HIP_OK(hipGetLastError());
             return;
         }
@@ -84,7 +84,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
                 hipLaunchKernelGGL(k4, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(256), d.lds_bytes,
                                    s, a.t0, (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B,
                                    C, (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit,
-                                   (uint32_t)d.row_base, a.ws, a.t2, stamps, ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)nullptr);
+                                   (uint32_t)d.row_base, a.ws, a.t2, stamps, ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)nullptr, epi);
                 HIP_OK(hipGetLastError());
                 return;
             } else {
@@ -137,6 +137,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
     if (d.ks_persist) {
         if constexpr (F16 && W == (int)kKsWaves && !STAMPS && (CT == 2 || CT == 8)) {
             GS_CHECK(d.ks_ap && !d.ks_p8 && !d.ks_wp && a.t3 && ks_col_tiles_ct(N, CT) == 1, "k_mfma_ks_persist: 8 waves, apart layout, 16-bit positions, one column tile");
+            GS_CHECK(gsk::epilogue_is_identity(epi), "k_mfma_ks_persist takes no epilogue (epilogue_fuses: the post-pass)");
             auto kp = d.ks_nt ? gsk::k_mfma_ks_persist<CT, RT, W, (int)kKsDepth, MAXG, 1>
                               : gsk::k_mfma_ks_persist<CT, RT, W, (int)kKsDepth, MAXG, 0>;
             grant_lds(d.device, kp, d.lds_bytes);
@@ -160,50 +161,52 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
     hipLaunchKernelGGL(kern, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(64 * W), d.lds_bytes, s, a.t0,
                        (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C,
                        (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit, (uint32_t)d.row_base, a.ws, a.t2, stamps,
-                       ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)a.tw);
+                       ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)a.tw, epi);
     HIP_OK(hipGetLastError());
 }
 
 template <int CT, int RT, class ET>
-void launch_ks_rt(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s) {
+void launch_ks_rt(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s,
+                  const gsk::epilogue &epi) {
     if constexpr (CT == 8) {  // 128-column tiles: only the (RT, MAXG) pairs that do not spill (ks_ct8_fits)
         GS_CHECK(ks_ct8_fits(RT, p.dev.seg_cap), "k_mfma_ks: 128-column tile instantiation not built for this plan");
         if constexpr (RT == 2) {
             switch (p.dev.seg_cap) {
-                case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
-                case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
-                default: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
+                case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
+                case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
+                default: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
             }
         } else {
-            launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s);
+            launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi);
         }
     } else {
         switch (p.dev.seg_cap) {  // MAXG: entry groups per lane per k-step
-            case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
-            case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
-            case 3: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
-            default: launch_ks_k<CT, RT, 4, false, (int)kKsWaves, ET>(p, a, B, C, N, s); break;
+            case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
+            case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
+            case 3: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
+            default: launch_ks_k<CT, RT, 4, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
         }
     }
 }
 
 template <int CT, class ET>
-void launch_ks_ct(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s) {
+void launch_ks_ct(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s,
+                  const gsk::epilogue &epi) {
     if constexpr (CT == 8) {  // 128 columns per workgroup: row blocks of up to 48 rows (ks_ct_rt)
         switch (p.dev.maxr) {
-            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s); return;
-            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s); return;
+            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s, epi); return;
+            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s, epi); return;
             default: throw gs_error("k_mfma_ks: 128-column tiles take row blocks of up to 48 rows");
         }
     } else {
         switch (p.dev.maxr) {  // RT: 16-row tiles per row block (the upload builds RT >= 2)
-            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s); break;
-            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s); break;
-            case 4: launch_ks_rt<CT, 4, ET>(p, a, B, C, N, s); break;
-            case 5: launch_ks_rt<CT, 5, ET>(p, a, B, C, N, s); break;
-            case 6: if constexpr (CT <= 2) { launch_ks_rt<CT, 6, ET>(p, a, B, C, N, s); break; } [[fallthrough]];
-            case 7: if constexpr (CT <= 2) { launch_ks_rt<CT, 7, ET>(p, a, B, C, N, s); break; } [[fallthrough]];
-            case 8: if constexpr (CT <= 2) { launch_ks_rt<CT, 8, ET>(p, a, B, C, N, s); break; } [[fallthrough]];
+            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s, epi); break;
+            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s, epi); break;
+            case 4: launch_ks_rt<CT, 4, ET>(p, a, B, C, N, s, epi); break;
+            case 5: launch_ks_rt<CT, 5, ET>(p, a, B, C, N, s, epi); break;
+            case 6: if constexpr (CT <= 2) { launch_ks_rt<CT, 6, ET>(p, a, B, C, N, s, epi); break; } [[fallthrough]];
+            case 7: if constexpr (CT <= 2) { launch_ks_rt<CT, 7, ET>(p, a, B, C, N, s, epi); break; } [[fallthrough]];
+            case 8: if constexpr (CT <= 2) { launch_ks_rt<CT, 8, ET>(p, a, B, C, N, s, epi); break; } [[fallthrough]];
             default: throw gs_error("k_mfma_ks: row tiles outside 2..8 (6..8 for N <= 32)");
         }
     }
@@ -370,6 +373,7 @@ void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStre
         e.pad0 = d.ks_gh;  // the entry's head-step group count (ks_body's prio bits 8..17)
         GS_CHECK(d.ks_wp == it[0].p->dev.ks_wp && (!d.ks_wp || a.tw), "k_mfma_ks_group: entries of different position forms");
         e.tW = (const uint8_t *)a.tw;
+        e.epi = it[i].epi;
         args.begin[i] = wg;
         // each entry starts on a multiple of 8 workgroups (idle ones in between exit at once), so
         // its entry-relative block numbers share XCDs as the global ones do (xcd_block)
@@ -407,29 +411,32 @@ void launch_ks_group_et(const std::vector<ks_group_item> &it, uint32_t N, hipStr
     }
 }
 template <class ET>
-void launch_ks_et(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
+void launch_ks_et(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+                  const gsk::epilogue &epi) {
     const ET *b = (const ET *)B;
     ET *c = (ET *)C;
     switch (p.dev.ks_ctw) {  // 16-column tiles per workgroup; ks_col_tiles_ct(N, CT) workgroups across N
-        case 1: launch_ks_ct<1, ET>(p, a, b, c, N, s); break;
-        case 2: launch_ks_ct<2, ET>(p, a, b, c, N, s); break;
-        case 4: launch_ks_ct<4, ET>(p, a, b, c, N, s); break;
-        case 8: launch_ks_ct<8, ET>(p, a, b, c, N, s); break;
+        case 1: launch_ks_ct<1, ET>(p, a, b, c, N, s, epi); break;
+        case 2: launch_ks_ct<2, ET>(p, a, b, c, N, s, epi); break;
+        case 4: launch_ks_ct<4, ET>(p, a, b, c, N, s, epi); break;
+        case 8: launch_ks_ct<8, ET>(p, a, b, c, N, s, epi); break;
         default: throw gs_error("k_mfma_ks: bad column tile count");
     }
 }
 }  // namespace
 
 #ifdef GS_KS_BF16_OBJECT
-void launch_ks_bf16(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
-    launch_ks_et<gsk::bf16>(p, a, B, C, N, s);
+void launch_ks_bf16(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+                    const gsk::epilogue &epi) {
+    launch_ks_et<gsk::bf16>(p, a, B, C, N, s, epi);
 }
 void launch_ks_group_bf16(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
     launch_ks_group_et<gsk::bf16>(it, N, s);
 }
 #else
 // the bf16 twins (ks_launch_bf16.o)
-void launch_ks_bf16(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
+void launch_ks_bf16(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+                    const gsk::epilogue &epi);
 void launch_ks_group_bf16(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s);
 
 uint32_t ks_group_key(const plan_state &p, uint32_t N) {
@@ -460,13 +467,14 @@ void launch_ks_group(const std::vector<ks_group_item> &it, uint32_t N, hipStream
     else launch_ks_group_et<gsk::f16>(it, N, s);
 }
 
-void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
+void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+               const gsk::epilogue &epi) {
     GS_CHECK(N == p.dev.lds_N, "k_mfma_ks runs the plan's dense width");
     GS_CHECK(p.dev.ks_ctw == ks_ct_rt(N, p.dev.maxr) || (p.dev.ks_ctw == 4 && ks_ct_rt(N, p.dev.maxr) == 8 &&
                                                          !ks_ct8_fits(p.dev.maxr, p.dev.seg_cap)),
              "k_mfma_ks: column tiles disagree with the upload");
-    if (p.dev.dtype == kBF16) launch_ks_bf16(p, a, B, C, N, s);
-    else launch_ks_et<gsk::f16>(p, a, B, C, N, s);
+    if (p.dev.dtype == kBF16) launch_ks_bf16(p, a, B, C, N, s, epi);
+    else launch_ks_et<gsk::f16>(p, a, B, C, N, s, epi);
 }
 
 #ifdef GS_EXPERIMENTS  // diagnostics (s_memtime stamps)

@@ -227,13 +227,15 @@ void launch_nm(const plan_state &p, const device_arrays &a, const void *B, void 
     }
 }
 
-void launch_mfma(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
+void launch_mfma(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+                 const gsk::epilogue &epi) {
     const gsk::f16 *b = (const gsk::f16 *)B;
     gsk::f16 *c = (gsk::f16 *)C;
     if (p.dev.ks) {
-        launch_ks(p, a, B, C, N, s);  // ks_launch.hip
+        launch_ks(p, a, B, C, N, s, epi);  // ks_launch.hip
         return;
     }
+    GS_CHECK(gsk::epilogue_is_identity(epi), "only k_mfma_ks applies an epilogue in the kernel (epilogue_fuses)");
     if (p.dev.bm) {
         launch_bm(p, a, B, C, N, s);  // ks_launch.hip
         return;

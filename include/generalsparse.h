@@ -129,6 +129,29 @@ int gs_plan_add_replica(gs_plan_t *p);
  * writable elements (the Python Plan.spmm / Rotation / Batch check their tensors). */
 int gs_spmm(gs_plan_t *p, const void *B, void *C, int N, gs_stream_t stream);
 int gs_spmm_replica(gs_plan_t *p, int replica, const void *B, void *C, int N, gs_stream_t stream);
+/* C = epilogue(A * B): gs_spmm_replica with an element-wise epilogue.  With acc the fp32 value of
+ * (A * B)[r][c], in this order: t = alpha * acc; t += bias[r] (bias: fp32 device array, one per row
+ * of C); t = t < 0 ? 0 : t (GS_ACT_RELU; NaN stays NaN); t += residual[r][c] (device array of the
+ * plan's dtype, M x N row-major, no overlap with C); C[r][c] = t rounded once to the plan's dtype.
+ * A stage with a NULL pointer / GS_ACT_NONE is skipped (alpha = 1 is exact).  epi NULL, or alpha 1
+ * with nothing else, runs exactly gs_spmm_replica's launches.
+ * Plans that run k_mfma_ks at their tile width apply it in the kernel's store, on the fp32 sums
+ * (gs_plan_epilogue_fused = 1); every other plan or width runs its kernels and then one in-place
+ * pass over C (k_epilogue; no allocation, legal under stream capture), which at GS_F16 / GS_BF16
+ * rounds twice: once by the family, once by the pass.  Config EPILOGUE_FUSE = 0 sends every plan
+ * through the pass.  Refused (GS_ERR) before any launch: an unknown activation, a non-finite
+ * alpha, residual == C. */
+enum { GS_ACT_NONE = 0, GS_ACT_RELU = 1 };
+typedef struct gs_epilogue {
+    float alpha;
+    int activation;         /* GS_ACT_NONE / GS_ACT_RELU */
+    const float *bias;      /* M fp32 values, or NULL */
+    const void *residual;   /* M x N elements of the plan's dtype, or NULL */
+} gs_epilogue;
+int gs_spmm_ex(gs_plan_t *p, int replica, const void *B, void *C, int N, const gs_epilogue *epi, gs_stream_t stream);
+/* 1: gs_spmm_ex at dense width N applies an epilogue inside the kernel (one rounding), 0: by the
+ * post-pass, < 0: error (the plan is not on the device) */
+int gs_plan_epilogue_fused(gs_plan_t *p, int N);
 /* `count` SpMMs enqueued back to back from native code, call i using replica
  * (first + i) % replicas with B_ptrs / C_ptrs entry (first + i) % n_ptrs
  * (bench rotation without a host round trip per launch) */
@@ -142,6 +165,13 @@ int gs_spmm_rotate(gs_plan_t *p, int count, int first, const void *const *B_ptrs
  * (k_mfma_ks_group); the others launch as gs_spmm_replica does. */
 int gs_spmm_batch(gs_plan_t *const *plans, const int *replicas, const void *const *B, void *const *C, int n, int N,
                   gs_stream_t stream);
+
+/* gs_spmm_batch with one epilogue per entry (epi NULL, or epi[i] NULL: none for that entry).  The
+ * launches are gs_spmm_batch's: an epilogue never splits a group; the entries of a grouped launch
+ * apply theirs in the kernel, a single entry as gs_spmm_ex does.  Every epilogue is checked before
+ * the first launch. */
+int gs_spmm_batch_ex(gs_plan_t *const *plans, const int *replicas, const void *const *B, void *const *C,
+                     const gs_epilogue *const *epi, int n, int N, gs_stream_t stream);
 
 /* how gs_spmm_batch would enqueue the batch: returns the number of launches (< 0: error) and
  * the entries each launch carries in entries_per_launch[0 .. min(count, cap)) (a grouped
