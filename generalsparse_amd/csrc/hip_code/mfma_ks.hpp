@@ -28,8 +28,10 @@ namespace gsk {
 // ds_read_b128), reads the RT A fragments and the CT B fragments, writes zeros back at
 // the entries' positions, and runs RT x CT v_mfma_f32_16x16x32_f16 into fp32
 // accumulators.  Every step issues the same loads (steps past the wave's last read the
-// first B rows and the spare group: one cached line each), so the compiler's waits
-// stay counted ones.  At the end the W partial tiles are summed through LDS in wave
+// first B rows and the spare group: one cached line each), and the prologue issues them
+// slot by slot in the loop's own order, so the compiler's waits stay counted ones: inside
+// the loop none goes below the L * (D - 1) loads of the other slots
+// (tests/test_ks_wait_counts.py).  At the end the W partial tiles are summed through LDS in wave
 // order; with S > 1 each workgroup publishes its fp32 slab (16-B sc1 write-through
 // stores, drained by every storing wave, then one arrival add), and the last of the row
 // block's S workgroups sums the S slabs in q order (deterministic, whichever arrives
@@ -71,6 +73,10 @@ __device__ constexpr int vmcnt_imm() {
 // GS_KS_FULL_TILE (1; 0 in a variant build for the A/B): the step loop's fast iterations, see ks_body
 #ifndef GS_KS_FULL_TILE
 #define GS_KS_FULL_TILE 1
+#endif
+// GS_KS_SLOT_ORDER (1; 0 in a variant build for the A/B): the prologue's load order, see ks_body
+#ifndef GS_KS_SLOT_ORDER
+#define GS_KS_SLOT_ORDER 1
 #endif
 enum : int { kKsPosU16 = 0, kKsPos8 = 1, kKsPosWin = 2 };
 template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, int PF = kKsPosU16, int NTL = 0, class ET = f16>
@@ -174,7 +180,34 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     // sit at (unit * min(W * D, NS) + step) * GH, padded with zero-row groups, so the prologue issues their
     // groups with the B rows at once instead of a record round trip later
     const uint32_t GH = (prio >> 8) & 0x3ffu;
-    if (GH) {
+    // GS_KS_SLOT_ORDER: both forms issue slot by slot in the step loop's own order -- a slot's B rows,
+    // its next record, its groups -- with scheduling barriers between the slots, so the queue at the
+    // loop's header is the steady state's and the loop's waits leave the other slots' loads in flight
+    if (GS_KS_SLOT_ORDER && GH) {
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            const uint32_t st = (uint32_t)d < nsw ? wv + (uint32_t)d * W : 0u;
+            load_b(std::false_type{}, (uint32_t)d, BR[d]);
+            __builtin_amdgcn_sched_barrier(0);
+            load_g_at((uint32_t)d, (u * min((uint32_t)(W * D), NS) + st) * GH, GH, NX[d], CN[d], P[d], V[d], WN[d]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        for (uint32_t x = lane; x < IMG / 16u; x += 64u) *reinterpret_cast<u32x4 *>(img + x * 16u) = zero4;
+        __builtin_amdgcn_sched_barrier(0);
+    } else if (GS_KS_SLOT_ORDER) {
+#pragma unroll
+        for (int d = 0; d < D; d++) NX[d] = rec_of((uint32_t)d);
+        __builtin_amdgcn_sched_barrier(0);
+        for (uint32_t x = lane; x < IMG / 16u; x += 64u) *reinterpret_cast<u32x4 *>(img + x * 16u) = zero4;
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            __builtin_amdgcn_sched_barrier(0);
+            load_b(std::false_type{}, (uint32_t)d, BR[d]);
+            __builtin_amdgcn_sched_barrier(0);
+            load_g((uint32_t)d, NX[d], CN[d], P[d], V[d], WN[d]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    } else if (GH) {
 #pragma unroll
         for (int d = 0; d < D; d++) load_b(std::false_type{}, (uint32_t)d, BR[d]);
 #pragma unroll

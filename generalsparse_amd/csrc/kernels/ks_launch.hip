@@ -54,11 +54,13 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
             }
         }
     }
-    // GS_KS_DEPTH=1/3/4 (look-ahead sweep against kKsDepth = 2, N = 32 on the C2 / attn / fc1 instantiations)
+    // GS_KS_DEPTH=1/3/4 (look-ahead sweep against kKsDepth = 2, N = 32 on the C2 / attn / fc1 instantiations and the
+    // layer's 112-row ones; plans uploaded with KS_HEAD = 0: the head-step layout is sized by kKsDepth)
     if constexpr (F16 && W == (int)kKsWaves && !STAMPS && CT == 2 &&
-                  ((RT == 3 && MAXG == 1) || (RT == 4 && MAXG == 2) || (RT == 5 && MAXG <= 2) || (RT == 7 && MAXG == 3))) {
+                  ((RT == 3 && MAXG == 1) || (RT == 4 && MAXG == 2) || (RT == 5 && MAXG <= 2) || (RT == 7 && MAXG >= 2))) {
         static const int dep = getenv("GS_KS_DEPTH") ? atoi(getenv("GS_KS_DEPTH")) : 0;
         if (dep == 1 || dep == 3 || dep == 4) {
+            GS_CHECK(!d.ks_gh && !d.ks_nt && !d.ks_wp, "GS_KS_DEPTH: upload the plan with KS_HEAD = 0, KS_NT = 0 and u16 positions");
             auto kd = dep == 1 ? gsk::k_mfma_ks<CT, RT, W, 1, MAXG, false>
                                : dep == 3 ? gsk::k_mfma_ks<CT, RT, W, 3, MAXG, false> : gsk::k_mfma_ks<CT, RT, W, 4, MAXG, false>;
             grant_lds(d.device, kd, d.lds_bytes);
