@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import GS_BF16, GS_F16, GS_F32, GsError
 
-__all__ = ["Plan", "Batch", "Rotation", "set_config", "GsError", "GS_F16", "GS_F32", "GS_BF16", "PIPELINES", "load_library",
+__all__ = ["Plan", "Batch", "Rotation", "SparseLinear", "set_config", "GsError", "GS_F16", "GS_F32", "GS_BF16", "PIPELINES", "load_library",
            "convert_values"]
 
 # token_test.cc pipelines (+ the two compositions this engine adds)
@@ -146,12 +146,13 @@ def _extent(t):
     return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
 
 
-def _epilogue(info, device, C, N, alpha=1.0, bias=None, activation=None, residual=None):
+def _epilogue(info, device, C, N, alpha=1.0, bias=None, activation=None, residual=None, token_major=False):
     """the gs_epilogue of one SpMM, or None for the identity (alpha 1, nothing else).  Everything is
     checked here, before any launch: the activation's name first, then alpha (finite), bias (a
     contiguous float32 GPU tensor of `rows` elements on `device`) and residual (a contiguous GPU
     tensor of C's dtype and shape on `device` whose memory does not overlap C's).  C: the output
-    tensor, (pointer, bytes) for a raw pointer, or None when spmm allocates it."""
+    tensor, (pointer, bytes) for a raw pointer, or None when spmm allocates it.  token_major
+    (Plan.linear): C and the residual are (N, rows), the bias still one per row of A."""
     act = _check_activation(activation)
     alpha = float(alpha)
     if not np.isfinite(alpha):
@@ -172,8 +173,9 @@ def _epilogue(info, device, C, N, alpha=1.0, bias=None, activation=None, residua
             raise ValueError(f"residual must be a GPU tensor on {device}")
         if residual.dtype != want:
             raise TypeError(f"residual must be {want}")
-        if not (tuple(residual.shape) == (rows, N) and residual.is_contiguous()):
-            raise ValueError(f"residual must be a contiguous tensor of shape ({rows}, {N})")
+        shape = (N, rows) if token_major else (rows, N)
+        if not (tuple(residual.shape) == shape and residual.is_contiguous()):
+            raise ValueError(f"residual must be a contiguous tensor of shape {shape}")
         if C is not None:
             (r0, r1), (c0, c1) = _extent(residual), _extent(C)
             if r0 < c1 and c0 < r1:
@@ -409,6 +411,47 @@ class Plan:
             _lib.check(k)
         return k
 
+    def linear(self, x, out=None, replica=0, stream=None, *, alpha=1.0, bias=None, activation=None, residual=None):
+        """y = epilogue(x @ A.T) on the GPU, with activations as a linear layer holds them (gs_linear):
+        x is a contiguous (n, K) GPU tensor of the plan's dtype, the result (n, M).  out and residual
+        are contiguous (n, M) tensors on x's device, residual not overlapping out; bias is float32
+        with M entries (one per output feature), so with A the (out, in) weight this is
+        F.linear(x, A, bias).  The stages and their order are spmm's.  linear_fused(n) tells whether
+        the call is one kernel on x and y in place or three launches through a transposed scratch.
+        Every argument is checked before anything is launched, so a refused call leaves out untouched."""
+        _check_activation(activation)
+        import torch
+        info = self.info()
+        want, M, K = _torch_dtype(info["dtype"]), info["rows"], info["cols"]
+        if not (x.is_cuda and x.dim() == 2 and x.is_contiguous()):
+            raise ValueError("x must be a contiguous 2-D GPU tensor")
+        if x.shape[1] != K:
+            raise ValueError(f"x has {x.shape[1]} columns, A has {K} columns")
+        if x.dtype != want:
+            raise TypeError(f"x must be {want}")
+        n = int(x.shape[0])
+        if n < 1:
+            raise ValueError("x holds no token")
+        if out is not None and not (out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == want
+                                    and tuple(out.shape) == (n, M)):
+            raise ValueError(f"out must be a contiguous {want} tensor of shape ({n}, {M}) on {x.device}")
+        epi = _epilogue(info, x.device, out, n, alpha, bias, activation, residual, token_major=True)
+        if out is None:
+            out = torch.empty((n, M), dtype=want, device=x.device)
+        s = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(self._L.gs_linear(self._h, int(replica), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), n,
+                                     ctypes.byref(epi) if epi is not None else None, ctypes.c_void_p(s)))
+        return out
+
+    def linear_fused(self, n):
+        """1 when linear at n tokens runs k_mfma_ks_tm (a k_mfma_ks plan at its own tile width of
+        17 .. 32 tokens, K a multiple of 8, LINEAR_FUSE on; x 16-byte aligned, as torch allocates),
+        0 when it runs the three-launch path; gs_plan_linear_fused"""
+        k = self._L.gs_plan_linear_fused(self._h, int(n))
+        if k < 0:
+            _lib.check(k)
+        return k
+
     def rotation(self, Bs, Cs):
         """the (B, C) pairs of spmm_rotate, checked and packed once; .run(count, first) enqueues"""
         return Rotation(self, Bs, Cs)
@@ -497,3 +540,11 @@ class Plan:
             self.free()
         except Exception:
             pass
+
+
+def __getattr__(name):
+    """SparseLinear lives in generalsparse_amd.nn, which needs torch: imported on first use"""
+    if name == "SparseLinear":
+        from .nn import SparseLinear
+        return SparseLinear
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

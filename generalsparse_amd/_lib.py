@@ -52,6 +52,9 @@ SIGNATURES = {
                           ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.POINTER(GsEpilogue)), ctypes.c_int,
                           ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "gs_plan_epilogue_fused": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
+    "gs_linear": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                   ctypes.POINTER(GsEpilogue), ctypes.c_void_p], ctypes.c_int),
+    "gs_plan_linear_fused": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "gs_plan_logical_check": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int], ctypes.c_int),
     "gs_plan_array_set_u64": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
     "gs_last_error": ([], ctypes.c_char_p),

@@ -70,6 +70,16 @@ GSK_HD constexpr size_t ks_lds_bytes(uint32_t CT, uint32_t RT, uint32_t W, bool 
     return stage > red ? stage : red;
 }
 
+// dynamic LDS of k_mfma_ks_tm (mfma_ks_tm.hpp; CT = 2): the W wave images and no B stage, then the W
+// partial tiles (+ the ticket word) when they fit beside the images, else in their place after a barrier
+GSK_HD constexpr bool ks_tm_red_apart(uint32_t RT, uint32_t W) {
+    return (size_t)W * (16u * RT + 1u) * kKsStride + (size_t)W * RT * 2u * 1024u + 16u <= 160u * 1024u;
+}
+GSK_HD constexpr size_t ks_tm_lds_bytes(uint32_t RT, uint32_t W) {
+    const size_t img = (size_t)W * (16u * RT + 1u) * kKsStride, red = (size_t)W * RT * 2u * 1024u + 16u;
+    return ks_tm_red_apart(RT, W) ? img + red : (img > red ? img : red);
+}
+
 // k_mfma_kb: the selector table (128 B) + W wave slots (one k-step of B rows + NVB KB of
 // values), then the W partial tiles (+ the ticket word) when they fit beside them
 GSK_HD constexpr size_t kb_stage_bytes(uint32_t CT, uint32_t W, uint32_t NVB) {

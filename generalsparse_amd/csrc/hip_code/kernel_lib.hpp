@@ -25,12 +25,15 @@
 //                       slot tree + a row carry per wave
 //   parts.hpp:
 //   k_combine_parts, k_add_parts, k_finalize_rows  element-wise companions of the above
+//   k_epilogue, k_tm_in, k_tm_out  the epilogue post-pass; the transposes around a plan's SpMM (gs_linear)
 //   lds_rows.hpp:
 //   k_lds_rows[_dma,_rs] K4 with B chunks staged in LDS, one workgroup per BMTB
 //   mfma_rows.hpp:
 //   k_mfma_rows      BMTB row blocks on the matrix cores, one workgroup per row block
 //   mfma_ks.hpp:
 //   k_mfma_ks[_group] the same with K split over workgroups
+//   mfma_ks_tm.hpp:
+//   k_mfma_ks_tm     a k_mfma_ks plan on token-major activations (gs_linear: Y = X * A^T)
 //   nm_mfma.hpp:
 //   k_nm_mfma        2:4 panels on the sparse matrix cores
 //   merge_path.hpp:
@@ -47,6 +50,7 @@
 #include "lds_rows.hpp"
 #include "mfma_rows.hpp"
 #include "mfma_ks.hpp"
+#include "mfma_ks_tm.hpp"
 #include "nm_mfma.hpp"
 #include "merge_path.hpp"
 #ifdef GS_EXPERIMENTS  // opt-in kernels measured slower than the default ones

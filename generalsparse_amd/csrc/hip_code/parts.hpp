@@ -1,6 +1,7 @@
 // hip_code/parts.hpp -- the element-wise companions of the other families: k_combine_parts
 // (parent-indexed sub-matrices), k_add_parts (MP_COL_PARTS), k_finalize_rows (fp32 workspace
-// rows) and k_epilogue (the epilogue as a post-pass).  Instantiated by kernels/device_plan.hip
+// rows), k_epilogue (the epilogue as a post-pass) and k_tm_in / k_tm_out (the transposes around a plan's
+// SpMM on gs_linear's three-launch path).  Instantiated by kernels/device_plan.hip
 // and kernels/gather_launch.hip.
 #pragma once
 
@@ -77,6 +78,42 @@ __global__ __launch_bounds__(256) void k_epilogue(VT *__restrict__ C, epilogue e
     }
     for (uint64_t e = first; e < total; e += stride)
         C[e] = (VT)epilogue_apply(epi, (float)C[e], e / N, res ? (float)res[e] : 0.f);
+}
+
+// The two ends of gs_linear's three-launch path (token-major activations around a plan's ordinary
+// SpMM): LDS-tiled transposes, a 32 x 32 tile per 256-thread workgroup (rows of 33 words: the
+// column reads are conflict-free), both sides of a tile read and written along their rows.
+// k_tm_in: B (K x N) = X^T, X: N x K.  blockIdx.x: the tile along K, blockIdx.y: along N.
+template <class VT>
+__global__ __launch_bounds__(256) void k_tm_in(const VT *__restrict__ X, VT *__restrict__ B, uint32_t K, uint32_t N) {
+    __shared__ VT tile[32][33];  // (the elements move as they are)
+    const uint32_t tx = threadIdx.x & 31u, ty = threadIdx.x >> 5;
+    const uint32_t k0 = blockIdx.x * 32u, n0 = blockIdx.y * 32u;
+    for (uint32_t r = ty; r < 32u; r += 8u)
+        if (n0 + r < N && k0 + tx < K) tile[r][tx] = X[(size_t)(n0 + r) * K + k0 + tx];
+    __syncthreads();
+    for (uint32_t r = ty; r < 32u; r += 8u)
+        if (k0 + r < K && n0 + tx < N) B[(size_t)(k0 + r) * N + n0 + tx] = tile[tx][r];
+}
+
+// k_tm_out: Y (N x M) = epilogue(C)^T, C: M x N as the plan's SpMM wrote it (acc = float(C): a 16-bit
+// plan rounds twice, as behind k_epilogue); bias[m] per row of C, the residual N x M as Y, read at
+// Y's index.  blockIdx.x: the tile along M, blockIdx.y: along N.
+template <class VT>
+__global__ __launch_bounds__(256) void k_tm_out(const VT *__restrict__ C, VT *__restrict__ Y, epilogue epi, uint32_t M,
+                                                uint32_t N) {
+    __shared__ float tile[32][33];
+    const uint32_t tx = threadIdx.x & 31u, ty = threadIdx.x >> 5;
+    const uint32_t m0 = blockIdx.x * 32u, n0 = blockIdx.y * 32u;
+    const VT *__restrict__ res = static_cast<const VT *>(epi.residual);
+    for (uint32_t r = ty; r < 32u; r += 8u)
+        if (m0 + r < M && n0 + tx < N) tile[r][tx] = (float)C[(size_t)(m0 + r) * N + n0 + tx];
+    __syncthreads();
+    for (uint32_t r = ty; r < 32u; r += 8u)
+        if (n0 + r < N && m0 + tx < M) {
+            const size_t at = (size_t)(n0 + r) * M + m0 + tx;
+            Y[at] = (VT)epilogue_apply(epi, tile[tx][r], m0 + tx, res ? (float)res[at] : 0.f);
+        }
 }
 
 }  // namespace gsk

@@ -33,7 +33,15 @@ struct parent_group {
     int device = 0;
 };
 
+// one plan replica's scratch of gs_linear's three-launch path: B (K x N) then C (M x N), N tokens
+struct linear_scratch {
+    void *buf = nullptr;
+    uint32_t N = 0;  // token count the buffer is sized for
+};
+
 struct gs_plan {
+    std::vector<linear_scratch> lin;  // per replica; allocated on first use, freed with the plan
+    int lin_device = 0;
     gs::plan_state st;
     std::map<int, std::unique_ptr<gs::plan_state>> subs;
     std::vector<std::pair<uint64_t, uint64_t>> gaps;  // output rows no sub-matrix writes
@@ -204,6 +212,50 @@ bool checked_epilogue(const gs_epilogue *e, const void *C, gsk::epilogue *out) {
     *out = gsk::epilogue{e->alpha, e->activation == GS_ACT_RELU ? gsk::kEpiRelu : gsk::kEpiNone, e->bias, e->residual};
     return !gsk::epilogue_is_identity(*out);
 }
+
+void free_linear(gs_plan *p) {
+    bool any = false;
+    for (auto &l : p->lin) any |= l.buf != nullptr;
+    if (any) (void)hipSetDevice(p->lin_device);
+    for (auto &l : p->lin)
+        if (l.buf) (void)hipFree(l.buf);
+    p->lin.clear();
+}
+
+// C's place behind B in that scratch: the next 256-byte boundary (the families' vector accesses)
+size_t linear_c_offset(uint64_t K, uint32_t N, size_t e) { return ((size_t)K * N * e + 255) / 256 * 256; }
+
+// replica `replica`'s scratch of gs_linear's three-launch path for N tokens: (K + M) x N elements,
+// allocated on first use and grown for a larger N (synchronous, so refused under stream capture: run
+// one call per replica and token count before capturing, as for the deferred CSR upload)
+linear_scratch &ensure_linear(gs_plan *p, int replica, uint32_t N, size_t e, int device, hipStream_t stream) {
+    if ((size_t)replica >= p->lin.size()) p->lin.resize((size_t)replica + 1);
+    linear_scratch &l = p->lin[(size_t)replica];
+    if (l.buf && l.N >= N) return l;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    GS_HIP(hipStreamIsCapturing(stream, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        throw gs::gs_error("gs_linear: the transposed operands of replica " + std::to_string(replica) + " at " +
+                               std::to_string(N) + " tokens are allocated on first use: call once before capturing",
+                           -2);
+    int prev = 0;
+    GS_HIP(hipGetDevice(&prev));
+    GS_HIP(hipSetDevice(device));
+    if (l.buf) {
+        // (a launch of this replica that still reads the smaller buffer: hipFree waits for the device)
+        (void)hipFree(l.buf);
+        l.buf = nullptr;
+        l.N = 0;
+    }
+    GS_HIP(hipMalloc(&l.buf, linear_c_offset(p->st.K, N, e) + (size_t)p->st.M * N * e));
+    l.N = N;
+    p->lin_device = device;
+    GS_HIP(hipSetDevice(prev));
+    return l;
+}
+
+// gs_linear's single launch applies: an undivided plan that k_mfma_ks_tm runs at this token count
+bool linear_fused(gs_plan *p, uint32_t n_tokens) { return !divided(p) && gs::linear_fuses(p->st, n_tokens); }
 
 }  // namespace
 
@@ -734,6 +786,7 @@ int gs_plan_upload(gs_plan_t *p, int dtype, int device) {
         for (gs::plan_state *s : ks) gs::upload_plan(*s, dtype, device);
         // parent-indexed sub-matrices, grouped by the row range they refer to
         free_groups(p);
+        free_linear(p);  // (the dtype or the device may have changed)
         for (gs::plan_state *s : ks) {
             if (s->parent_row_base < 0) continue;
             auto g = std::find_if(p->groups.begin(), p->groups.end(), [&](const parent_group &x) {
@@ -801,6 +854,48 @@ int gs_plan_epilogue_fused(gs_plan_t *p, int N) {
         GS_CHECK(p && N > 0, "bad argument");
         GS_CHECK(divided(p) || p->st.uploaded, "plan is not on the device");
         fused = !divided(p) && gs::epilogue_fuses(p->st, (uint32_t)N) ? 1 : 0;
+    });
+    return rc < 0 ? rc : fused;
+}
+
+int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, const gs_epilogue *epi, gs_stream_t stream) {
+    return guard([&] {
+        GS_CHECK(p && X && Y && n_tokens >= 1, "bad argument");
+        // every check before any launch: gs_spmm_ex's, the replica and the residual's whole extent too
+        auto ks = kernel_states(p);
+        for (gs::plan_state *s : ks) {
+            GS_CHECK(s->uploaded, "plan is not on the device");
+            GS_CHECK(replica >= 0 && (size_t)replica < s->dev.replicas.size(), "bad replica index");
+        }
+        gsk::epilogue e = gsk::epilogue_identity();
+        checked_epilogue(epi, Y, &e);
+        const int dtype = ks.front()->dev.dtype;
+        const size_t eb = gs::elem_bytes(dtype);
+        const uint32_t N = (uint32_t)n_tokens;
+        if (e.residual) {
+            const uintptr_t bytes = (uintptr_t)p->st.M * N * eb, r = (uintptr_t)e.residual, y = (uintptr_t)Y;
+            GS_CHECK(r + bytes <= y || y + bytes <= r, "gs_epilogue: the residual may not overlap Y");
+        }
+        hipStream_t s = (hipStream_t)stream;
+        if (linear_fused(p, N) && (uintptr_t)X % 16 == 0) {
+            gs::launch_linear_fused(p->st, replica, X, Y, N, s, e);
+            return;
+        }
+        // every other plan, width and alignment: X -> B (K x N), the plan's launches into C (M x N),
+        // the epilogue and the way back in k_tm_out
+        linear_scratch &l = ensure_linear(p, replica, N, eb, ks.front()->dev.device, s);
+        void *B = l.buf, *C = (char *)l.buf + linear_c_offset(p->st.K, N, eb);
+        gs::launch_tm_in(X, B, p->st.K, N, dtype, s);
+        spmm_all(p, replica, B, C, N, s, nullptr);
+        gs::launch_tm_out(C, Y, p->st.M, N, dtype, e, s);
+    });
+}
+
+int gs_plan_linear_fused(gs_plan_t *p, int n_tokens) {
+    int fused = 0;
+    const int rc = guard([&] {
+        GS_CHECK(p && n_tokens > 0, "bad argument");
+        fused = linear_fused(p, (uint32_t)n_tokens) ? 1 : 0;
     });
     return rc < 0 ? rc : fused;
 }
@@ -1128,6 +1223,7 @@ void gs_plan_free(gs_plan_t *p) {
     if (!p) return;
     try {
         free_groups(p);
+        free_linear(p);
         gs::free_device(p->st);
         for (auto &kv : p->subs) gs::free_device(*kv.second);
     } catch (...) {

@@ -96,6 +96,9 @@ inline uint32_t ks_ct_rt(uint32_t N, uint32_t RT) { return N >= 128 && RT <= 3 ?
 // ... and the 128-column instantiations that hold their registers (no spill): 32-row blocks with up to
 // 192 entry groups per k-step, 48-row blocks with up to 64; other plans at N >= 128 take CT = 4
 inline bool ks_ct8_fits(uint32_t RT, uint32_t MAXG) { return (RT == 2 && MAXG <= 3) || (RT == 3 && MAXG == 1); }
+// k_mfma_ks_tm (gs_linear's single launch; 32-token tiles): the (RT, MAXG) instantiations that are built --
+// those that hold their registers (the kernel's resource table); other plans take the three-launch path
+constexpr bool ks_tm_fits(uint32_t RT, uint32_t MAXG) { return RT >= 2 && RT <= 8 && MAXG >= 1 && MAXG <= 4; }
 inline uint32_t ks_col_tiles_ct(uint32_t N, uint32_t CT) { return (N + 16 * CT - 1) / (16 * CT); }
 
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,

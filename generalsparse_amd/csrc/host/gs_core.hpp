@@ -125,6 +125,8 @@ struct config_t {
                                  // group lies in one window).  Other shapes keep the u16 layout
     int64_t EPILOGUE_FUSE = 1;   // an epilogue (gs_spmm_ex) of a k_mfma_ks plan at its tile width: 1 in the kernel's
                                  // store (one rounding), 0 the post-pass k_epilogue every other family takes (the A/B)
+    int64_t LINEAR_FUSE = 1;     // gs_linear on a k_mfma_ks plan that k_mfma_ks_tm covers: 1 that kernel (one launch, one
+                                 // rounding), 0 the three-launch path every other plan takes (the A/B, the tests)
     int64_t KS_HEAD = 1;        // k_mfma_ks: the head steps (each wave's first kKsDepth k-steps) at fixed, padded
                                  // places, loaded without their records (when the padding costs <= 6% more groups)
     int64_t KS_PERSIST = 0;      // k_mfma_ks: persistent grid size pulling (row block, K range) units (experiments build)

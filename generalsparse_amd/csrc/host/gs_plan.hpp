@@ -171,6 +171,18 @@ void launch_gather(const plan_state &p, const device_arrays &a, const void *B, v
 // ks_launch.hip: k_mfma_ks (K-split, wave-autonomous matrix-core row blocks)
 void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
                const gsk::epilogue &epi = gsk::epilogue_identity());
+// ks_tm_launch.hip: k_mfma_ks_tm, a k_mfma_ks plan on token-major activations (gs_linear: Y = X * A^T,
+// X: n_tokens x K, Y: n_tokens x M).  linear_fuses: the plan, its upload layout and the width are ones
+// the kernel is built for (32-token tiles at the plan's own width, 8 waves, 16-bit positions, K % 8 == 0,
+// LINEAR_FUSE on); the launch needs X 16-byte aligned as well.  Allocates nothing
+bool linear_fuses(const plan_state &p, uint32_t n_tokens);
+void launch_linear_fused(const plan_state &p, int replica, const void *X, void *Y, uint32_t n_tokens, hipStream_t s,
+                         const gsk::epilogue &epi);
+// device_plan.hip: the two ends of gs_linear's three-launch path (parts.hpp k_tm_in / k_tm_out)
+// B (K x N) = X^T (X: N x K)
+void launch_tm_in(const void *X, void *B, uint64_t K, uint32_t N, int dtype, hipStream_t stream);
+// Y (N x M) = epilogue(C)^T (C: M x N; the residual N x M, as Y)
+void launch_tm_out(const void *C, void *Y, uint64_t M, uint32_t N, int dtype, const gsk::epilogue &epi, hipStream_t stream);
 // grouped k_mfma_ks launches (gs_spmm_batch): one grid over up to 32 entries of one
 // instantiation (equal nonzero ks_group_key); every entry a distinct (plan, replica)
 struct ks_group_item {

@@ -838,6 +838,30 @@ void launch_epilogue(void *C, uint64_t rows, uint32_t N, int dtype, const gsk::e
     HIP_OK(hipGetLastError());
 }
 
+void launch_tm_in(const void *X, void *B, uint64_t K, uint32_t N, int dtype, hipStream_t stream) {
+    GS_CHECK(K >= 1 && N >= 1 && K < (1ull << 32) && (N + 31) / 32 <= 65535u, "launch_tm_in: bad sizes");
+    const dim3 grid((uint32_t)((K + 31) / 32), (N + 31) / 32);
+    if (dtype == kF32)
+        hipLaunchKernelGGL(gsk::k_tm_in<float>, grid, dim3(256), 0, stream, (const float *)X, (float *)B, (uint32_t)K, N);
+    else  // (the 16-bit types move as words)
+        hipLaunchKernelGGL(gsk::k_tm_in<uint16_t>, grid, dim3(256), 0, stream, (const uint16_t *)X, (uint16_t *)B, (uint32_t)K, N);
+    HIP_OK(hipGetLastError());
+}
+
+void launch_tm_out(const void *C, void *Y, uint64_t M, uint32_t N, int dtype, const gsk::epilogue &epi, hipStream_t stream) {
+    GS_CHECK(M >= 1 && N >= 1 && M < (1ull << 32) && (N + 31) / 32 <= 65535u, "launch_tm_out: bad sizes");
+    const dim3 grid((uint32_t)((M + 31) / 32), (N + 31) / 32);
+    if (dtype == kF32)
+        hipLaunchKernelGGL(gsk::k_tm_out<float>, grid, dim3(256), 0, stream, (const float *)C, (float *)Y, epi, (uint32_t)M, N);
+    else if (dtype == kBF16)
+        hipLaunchKernelGGL(gsk::k_tm_out<gsk::bf16>, grid, dim3(256), 0, stream, (const gsk::bf16 *)C, (gsk::bf16 *)Y, epi,
+                           (uint32_t)M, N);
+    else
+        hipLaunchKernelGGL(gsk::k_tm_out<gsk::f16>, grid, dim3(256), 0, stream, (const gsk::f16 *)C, (gsk::f16 *)Y, epi,
+                           (uint32_t)M, N);
+    HIP_OK(hipGetLastError());
+}
+
 static void launch_body(plan_state &p, int replica, const void *B, void *C, uint32_t N, hipStream_t stream,
                         const gsk::epilogue &epi) {
     // (the upload builds no other layout for a bf16 plan: choose_matrix_core_layout, LDS_STAGE_B)

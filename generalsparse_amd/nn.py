@@ -1,0 +1,85 @@
+"""torch.nn modules over the engine: SparseLinear, a pruned linear layer run by Plan.linear.
+
+    layer = SparseLinear.from_dense(weight, bias, tokens=32, activation="relu")   # weight: (out, in), pruned
+    y = layer(x)                                                                     # x: (..., in) -> (..., out)
+
+Inference only: the engine has no backward pass."""
+import numpy as np
+import torch
+
+from . import Plan, _check_activation, _dtype_code, _torch_dtype
+
+
+class SparseLinear(torch.nn.Module):
+    """y = activation(x @ W.T + bias) [+ residual] with W held as a compiled, uploaded Plan
+    (gs_linear: activations token-major, as torch holds them, no transposes around the SpMM).
+    plan: an uploaded Plan of the (out, in) weight; bias: None or `out` values (kept as a float32
+    buffer on the plan's device); activation: None or "relu"."""
+
+    def __init__(self, plan, bias=None, activation=None):
+        super().__init__()
+        _check_activation(activation)  # before anything touches a device
+        self.plan, self.activation = plan, activation
+        info = plan.info()
+        self.in_features, self.out_features = int(info["cols"]), int(info["rows"])
+        self.tokens = int(info["lds_n"]) or None  # the width the plan's tiles were built for
+        if bias is not None:
+            bias = torch.as_tensor(bias).detach().to(torch.float32).reshape(-1).contiguous()
+            if bias.numel() != self.out_features:
+                raise ValueError(f"bias must hold {self.out_features} values (one per output feature)")
+        self.register_buffer("bias", bias)
+
+    @classmethod
+    def from_dense(cls, weight, bias=None, *, tokens=32, dtype="f16", pipeline=("block_total", 40, 1), activation=None,
+                   device=0, upload=True):
+        """the plan from the non-zeros of a pruned (out, in) weight: from_coo, run_pipeline at
+        N = tokens, compile, upload (upload=False stops before the device: the plan can be inspected,
+        the module cannot run)"""
+        _check_activation(activation)
+        _dtype_code(dtype)
+        w = torch.as_tensor(weight).detach().to("cpu", torch.float32).numpy()
+        if w.ndim != 2:
+            raise ValueError("weight must be (out_features, in_features)")
+        r, c = np.nonzero(w)  # row-major order: row-sorted, columns sorted inside a row
+        name, p0, p1 = pipeline
+        plan = Plan.from_coo(w.shape[0], w.shape[1], r.astype(np.uint64), c.astype(np.uint64), w[r, c])
+        plan.run_pipeline(name, int(tokens), int(p0), int(p1)).compile()
+        if upload:
+            plan.upload(dtype, int(device))
+            if bias is not None:
+                bias = torch.as_tensor(bias).detach().to(torch.device("cuda", int(device)), torch.float32)
+        layer = cls(plan, bias, activation)
+        layer.tokens = int(tokens)
+        return layer
+
+    def forward(self, x, residual=None):
+        """x: (..., in_features) of the plan's dtype on its device -> (..., out_features); the leading
+        dimensions are flattened into the token count.  residual: (..., out_features), added last."""
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("SparseLinear is inference only (no backward pass): run it under torch.no_grad() "
+                               "or on a tensor that does not require grad")
+        if x.dim() < 1 or x.shape[-1] != self.in_features:
+            raise ValueError(f"x must be (..., {self.in_features})")
+        lead = tuple(x.shape[:-1])
+        x2 = x.reshape(-1, self.in_features)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        if residual is not None:
+            if tuple(residual.shape) != lead + (self.out_features,):
+                raise ValueError(f"residual must be {lead + (self.out_features,)}")
+            residual = residual.reshape(-1, self.out_features)
+            if not residual.is_contiguous():
+                residual = residual.contiguous()
+        y = self.plan.linear(x2, bias=self.bias, activation=self.activation, residual=residual)
+        return y.reshape(lead + (self.out_features,))
+
+    def extra_repr(self):
+        info = self.plan.info()
+        kernel = info["device_kernel"] or info["kernel_name"]
+        s = f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
+            f"activation={self.activation!r}, kernel={kernel}"
+        if self.tokens:
+            s += f", linear_fused({self.tokens})={self.plan.linear_fused(self.tokens)}"
+        if info["replicas"]:
+            s += f", dtype={_torch_dtype(info['dtype'])}"
+        return s

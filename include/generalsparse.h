@@ -152,6 +152,26 @@ int gs_spmm_ex(gs_plan_t *p, int replica, const void *B, void *C, int N, const g
 /* 1: gs_spmm_ex at dense width N applies an epilogue inside the kernel (one rounding), 0: by the
  * post-pass, < 0: error (the plan is not on the device) */
 int gs_plan_epilogue_fused(gs_plan_t *p, int N);
+/* Y = epilogue(X * A^T).  X: n_tokens x K, Y: n_tokens x M, row-major, the plan's dtype.
+ * epi may be NULL; bias is per column of Y (row of A); residual is n_tokens x M, no overlap with Y.
+ * The layout a linear layer holds its activations in: with A the (out, in) weight this is
+ * F.linear(X, A, bias), the epilogue's stages in gs_spmm_ex's order on the fp32 sums.
+ * A k_mfma_ks plan at its own tile width of 17 .. 32 tokens (8 waves, 16-bit positions, no row padding),
+ * K % 8 == 0 and X 16-byte aligned runs ONE kernel, k_mfma_ks_tm, on the plan as uploaded: X is read
+ * and Y written in place, the epilogue is applied in the store (one rounding), nothing is allocated
+ * (gs_plan_linear_fused = 1).  Every other plan, width and alignment runs three launches: X
+ * transposed into a scratch B, the plan's gs_spmm_replica launches, and the epilogue with the
+ * transpose back (at GS_F16 / GS_BF16 two roundings, as gs_spmm_ex's pass).  The scratch of (K + M) x
+ * n_tokens elements belongs to the plan replica; it is allocated by the first call at a token count
+ * (grown for a larger one, freed with the plan), synchronously: inside stream capture that first call
+ * is refused, later ones are legal.  Config LINEAR_FUSE = 0 sends every plan through the three
+ * launches; EPILOGUE_FUSE is not consulted.  Refused (GS_ERR) before any launch: a plan that is not
+ * on the device, a bad replica, n_tokens < 1, an unknown activation, a non-finite alpha, a
+ * residual that overlaps Y anywhere in its n_tokens x M elements. */
+int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, const gs_epilogue *epi, gs_stream_t stream);
+/* 1: gs_linear at n_tokens runs k_mfma_ks_tm (given an aligned X), 0: the three-launch path (also for a
+ * plan that is not on the device), < 0: error */
+int gs_plan_linear_fused(gs_plan_t *p, int n_tokens);
 /* `count` SpMMs enqueued back to back from native code, call i using replica
  * (first + i) % replicas with B_ptrs / C_ptrs entry (first + i) % n_ptrs
  * (bench rotation without a host round trip per launch) */
