@@ -418,6 +418,9 @@ class Plan:
         with M entries (one per output feature), so with A the (out, in) weight this is
         F.linear(x, A, bias).  The stages and their order are spmm's.  linear_fused(n) tells whether
         the call is one kernel on x and y in place or three launches through a transposed scratch.
+        On a plan that kernel covers (a k_mfma_ks plan built for 17 .. 32 tokens) any n >= 1 runs it,
+        on ceil(n / 32) token tiles, and row t of y has the same bits whatever n is and wherever
+        token t stands in x; linear_launches(n) tells the launches.
         Every argument is checked before anything is launched, so a refused call leaves out untouched."""
         _check_activation(activation)
         import torch
@@ -444,13 +447,33 @@ class Plan:
         return out
 
     def linear_fused(self, n):
-        """1 when linear at n tokens runs k_mfma_ks_tm (a k_mfma_ks plan at its own tile width of
-        17 .. 32 tokens, K a multiple of 8, LINEAR_FUSE on; x 16-byte aligned, as torch allocates),
-        0 when it runs the three-launch path; gs_plan_linear_fused"""
+        """1 when linear at n tokens runs k_mfma_ks_tm (a k_mfma_ks plan built for 17 .. 32 tokens,
+        K a multiple of 8, LINEAR_FUSE on; x 16-byte aligned, as torch allocates) -- for such a plan
+        at every n >= 1, not only the width it was built for -- 0 when it runs the three-launch
+        path; gs_plan_linear_fused"""
         k = self._L.gs_plan_linear_fused(self._h, int(n))
         if k < 0:
             _lib.check(k)
         return k
+
+    def linear_launches(self, n, x=None):
+        """the k_mfma_ks_tm launches linear enqueues at n tokens: a list of token tiles (of 32 tokens)
+        per launch, in token order -- [ceil(n / 32)] unless the tiles' K-split state would pass
+        LINEAR_WS_KB; [] for the three-launch path.  x (optional): the tensor linear would get; one
+        that is not 16-byte aligned takes the three launches (without it, alignment is assumed);
+        gs_plan_linear_launches"""
+        if x is not None and x.data_ptr() % 16:
+            self.linear_fused(n)  # (the plan's own errors first)
+            return []
+        cap = 16
+        while True:
+            buf = (ctypes.c_int * cap)()
+            k = self._L.gs_plan_linear_launches(self._h, int(n), buf, cap)
+            if k < 0:
+                _lib.check(k)
+            if k <= cap:
+                return list(buf[:k])
+            cap = k
 
     def rotation(self, Bs, Cs):
         """the (B, C) pairs of spmm_rotate, checked and packed once; .run(count, first) enqueues"""

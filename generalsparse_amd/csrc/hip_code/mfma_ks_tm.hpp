@@ -18,6 +18,11 @@ namespace gsk {
 // the W partial tiles are summed through LDS in wave order; with S > 1 the ticket, the tagged slabs
 // and the last ticket holder's combine in q order (ks_slab_wait).  The MFMAs, their order and the
 // order of every sum are k_mfma_ks's, so Y is bit for bit the transpose of its C.
+// Any token count N >= 1: T = ceil(N / 32) token tiles in one launch, the last one partial; a tile's
+// workgroups see nothing of the others', so row t of Y does not depend on N nor on where token t
+// stands.  With S > 1 the slabs and the arrival counters are laid out by T (slab of (unit, tile) at
+// u * T + tile, counter of (row block, tile) at g * T + tile, the error word behind the nb * T
+// counters): the caller passes state of that layout (ks_tm_launch.hip, gs_linear).
 // What differs:
 // - B side.  The MFMA's B operand of lane l is column l % 16, k = 8 * (l / 16) .. + 7: with X[n][k] these
 //   are 16 contiguous bytes of token col0 + 16 * ct + l % 16 at k0 + 32 * st + 8 * (l / 16), loaded from
@@ -49,11 +54,25 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t u = xcd_block(blockIdx.x, nwg);
+    // T token tiles per unit on a 1-D grid of nwg * T workgroups (T in prio's bits 18..31; 0 reads as 1):
+    // unit-major, v = u * T + tile, so the T tiles of one unit are neighbours in dispatch order on one
+    // XCD and share the unit's A stream through that L2.  T = 1: v = u, the grid of before
+    const uint32_t T = max(prio >> 18, 1u);
+    uint32_t u = xcd_block(blockIdx.x, nwg * T), tile = 0;
+    if (T > 1u) {
+        const uint32_t v = u;
+#if defined(GS_EXPERIMENTS) && defined(GS_KS_TM_TILE_MAJOR)  // A/B: all units of tile 0, then tile 1, ...
+        tile = v / nwg;
+        u = v - tile * nwg;
+#else
+        u = v / T;
+        tile = v - u * T;
+#endif
+    }
     const uint32_t g = u / S, q = u - g * S;
     const uint32_t k0 = q * NS * 32u;
-    // token tile blockIdx.y: tokens [col0, col0 + nv) of X and Y (N = 24: one partial tile)
-    const uint32_t col0 = blockIdx.y * 16u * CT, nv = min(16u * CT, N - col0);
+    // token tile `tile`: tokens [col0, col0 + nv) of X and Y (N = 24: one partial tile)
+    const uint32_t col0 = tile * 16u * CT, nv = min(16u * CT, N - col0);
     unsigned char *img = lds + wv * IMG;
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
@@ -71,11 +90,15 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     };
     // the lane's 16-byte unit of a k-step: token 16 * c + lane % 16 of the tile, k = 8 * (lane / 16) .. + 7
     const uint32_t ku = 8u * (lane >> 4);
-    // FAST (the loop's fast iterations, below): the step's 32 columns of X lie below K and the token
-    // tile is full, so the address is a scalar k term plus the lane's offset
+    // FAST (the loop's fast iterations, below): the step's 32 columns of X lie below K, so the address
+    // is a scalar k term plus the lane's offset; the offset of a token past N in a partial tile is the
+    // tile's first token's (its accumulators are never stored)
     uint32_t xoff[CT];
 #pragma unroll
-    for (int c = 0; c < CT; c++) xoff[c] = (16u * c + (lane & 15u)) * K + ku;
+    for (int c = 0; c < CT; c++) {
+        const uint32_t tk = 16u * c + (lane & 15u);
+        xoff[c] = (tk < nv ? tk : 0u) * K + ku;
+    }
     auto load_b = [&](auto fast, uint32_t i, u32x4 (&B_)[CT]) {
         const uint32_t st = __builtin_amdgcn_readfirstlane(i < nsw ? wv + i * W : 0u);
         const uint32_t kr = k0 + st * 32u;  // first column of X of the step
@@ -201,8 +224,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(1);
     const uint32_t fsp = min(NS, K > k0 ? (K - k0) / 32u : 0u);
     const uint32_t nfull = fsp > wv ? (fsp - wv + W - 1u) / W : 0u;  // this wave's full steps
-    uint32_t fast_end = 0;
-    if (nv == 16u * CT) fast_end = fsp == NS ? nsw : (nfull >= 2u * D ? ((nfull - 2u * D) / D + 1u) * D : 0u);
+    uint32_t fast_end = fsp == NS ? nsw : (nfull >= 2u * D ? ((nfull - 2u * D) / D + 1u) * D : 0u);
     fast_end = __builtin_amdgcn_readfirstlane(fast_end);
     uint32_t i0 = 0;
     for (; i0 < fast_end; i0 += D) {
@@ -217,7 +239,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     }
     if ((prio & 3u) && young) __builtin_amdgcn_s_setprio(0);
     // ---- K-split ticket, taken as soon as wave 0's loop ends (ks_body)
-    uint32_t *arr = arrivals + (size_t)g * gridDim.y + blockIdx.y;
+    uint32_t *arr = arrivals + (size_t)g * T + tile;
     uint32_t ticket = 0;
     if (S > 1 && wv == 0 && lane == 0) ticket = __hip_atomic_fetch_add(arr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // ---- wave partial tiles -> LDS, summed in wave order.  Item t = (tile, lane) of a 16x16 tile: the
@@ -281,7 +303,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     // ---- K-split combine by tagged slabs: ks_body's, word for word (the slabs, the tags, the
     // arrival counter's epoch and the device error word are the plan replica's, shared with k_mfma_ks)
     const uint32_t tk = *flag & 0xffffu, tag = ((*flag >> 16) & 1u) ^ 1u;
-    f4v *slab = reinterpret_cast<f4v *>(slabs) + ((size_t)u * gridDim.y + blockIdx.y) * NI;
+    f4v *slab = reinterpret_cast<f4v *>(slabs) + ((size_t)u * T + tile) * NI;
     auto tagged = [&](const f4v &v) {
         u32x4 w;
         __builtin_memcpy(&w, &v, 16);
@@ -294,9 +316,9 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     }
     if (tk != S - 1u) return;
     if (tid == 0) __hip_atomic_store(arr, tag << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const f4v *base = reinterpret_cast<const f4v *>(slabs) + blockIdx.y * NI;
-    const size_t qstride = (size_t)gridDim.y * NI;  // slab of (g, qq) = base + (g*S + qq) * qstride
-    uint32_t *err = arrivals + (size_t)(nwg / S) * gridDim.y;  // the replica's device error word
+    const f4v *base = reinterpret_cast<const f4v *>(slabs) + tile * NI;
+    const size_t qstride = (size_t)T * NI;  // slab of (g, qq) = base + (g*S + qq) * qstride
+    uint32_t *err = arrivals + (size_t)(nwg / S) * T;  // the replica's device error word
     for (uint32_t t = tid; t < NI; t += NT) {
         f4v sum = {0.f, 0.f, 0.f, 0.f};
         for (uint32_t qq = 0; qq < S; qq++) {

@@ -39,8 +39,21 @@ struct linear_scratch {
     uint32_t N = 0;  // token count the buffer is sized for
 };
 
+// one plan replica's K-split state of gs_linear's k_mfma_ks_tm launches of more than one token tile
+// (a single tile runs on the upload's own): [slabs of `cap` tiles][nb * cap arrival counters][the
+// device error word].  A launch of T tiles takes the first T tiles' slabs and the LAST nb * T counters,
+// so the error word -- which the kernel finds right behind its counters -- has one address
+struct linear_ks_state {
+    void *buf = nullptr;
+    uint32_t *err = nullptr;  // the error word, inside buf
+    uint32_t cap = 0;         // tiles the buffer holds
+    uint32_t last = 0;        // tile count whose layout the counters' epochs and the slabs' tags belong to (0: unknown)
+    bool captured = false;    // a captured launch may replay between any two calls: `last` is never known again
+};
+
 struct gs_plan {
     std::vector<linear_scratch> lin;  // per replica; allocated on first use, freed with the plan
+    std::vector<linear_ks_state> lin_ks;  // per replica, likewise
     int lin_device = 0;
     gs::plan_state st;
     std::map<int, std::unique_ptr<gs::plan_state>> subs;
@@ -216,10 +229,14 @@ bool checked_epilogue(const gs_epilogue *e, const void *C, gsk::epilogue *out) {
 void free_linear(gs_plan *p) {
     bool any = false;
     for (auto &l : p->lin) any |= l.buf != nullptr;
+    for (auto &l : p->lin_ks) any |= l.buf != nullptr;
     if (any) (void)hipSetDevice(p->lin_device);
     for (auto &l : p->lin)
         if (l.buf) (void)hipFree(l.buf);
+    for (auto &l : p->lin_ks)
+        if (l.buf) (void)hipFree(l.buf);
     p->lin.clear();
+    p->lin_ks.clear();
 }
 
 // C's place behind B in that scratch: the next 256-byte boundary (the families' vector accesses)
@@ -256,6 +273,72 @@ linear_scratch &ensure_linear(gs_plan *p, int replica, uint32_t N, size_t e, int
 
 // gs_linear's single launch applies: an undivided plan that k_mfma_ks_tm runs at this token count
 bool linear_fused(gs_plan *p, uint32_t n_tokens) { return !divided(p) && gs::linear_fuses(p->st, n_tokens); }
+
+// the k_mfma_ks_tm launches of an n-token gs_linear on a plan linear_fused admits: token tiles per
+// launch, in token order (LINEAR_WS_KB bounds the K-split state of one launch)
+std::vector<uint32_t> linear_tiles(gs_plan *p, uint32_t n_tokens) {
+    const gs::device_plan &d = p->st.dev;
+    return gs::ks_tm_tile_split(n_tokens, gs::ks_tm_tile_cap(d.n_rows_aux, d.ksplit, d.maxr, gs::get_config().LINEAR_WS_KB));
+}
+
+bool capturing(hipStream_t stream) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    GS_HIP(hipStreamIsCapturing(stream, &cap));
+    return cap != hipStreamCaptureStatusNone;
+}
+
+// replica `replica`'s K-split state for launches of up to T token tiles (linear_ks_state): allocated on
+// first use and grown for a larger T, by ensure_linear's rules (synchronous, refused under capture)
+linear_ks_state &ensure_linear_ks(gs_plan *p, int replica, uint32_t T, hipStream_t stream) {
+    if ((size_t)replica >= p->lin_ks.size()) p->lin_ks.resize((size_t)replica + 1);
+    linear_ks_state &l = p->lin_ks[(size_t)replica];
+    if (l.buf && l.cap >= T) return l;
+    if (capturing(stream))
+        throw gs::gs_error("gs_linear: the K-split state of replica " + std::to_string(replica) + " for " + std::to_string(T) +
+                               " token tiles is allocated on first use: call once before capturing",
+                           -2);
+    const gs::device_plan &d = p->st.dev;
+    const size_t slab = (size_t)d.n_rows_aux * d.ksplit * d.maxr * 2048u, ctr = (size_t)d.n_rows_aux * sizeof(uint32_t);
+    int prev = 0;
+    GS_HIP(hipGetDevice(&prev));
+    GS_HIP(hipSetDevice(d.device));
+    uint32_t word = 0;  // a fault not yet reported moves to the larger buffer
+    if (l.buf) {
+        // (a launch of this replica that still uses the smaller buffer: wait for the device)
+        GS_HIP(hipDeviceSynchronize());
+        GS_HIP(hipMemcpy(&word, l.err, sizeof(word), hipMemcpyDeviceToHost));
+        (void)hipFree(l.buf);
+        l = linear_ks_state();
+    }
+    GS_HIP(hipMalloc(&l.buf, (slab + ctr) * T + sizeof(uint32_t)));
+    l.err = reinterpret_cast<uint32_t *>((char *)l.buf + (slab + ctr) * T);
+    GS_HIP(hipMemcpy(l.err, &word, sizeof(word), hipMemcpyHostToDevice));
+    l.cap = T;
+    p->lin_device = d.device;
+    GS_HIP(hipSetDevice(prev));
+    return l;
+}
+
+// one k_mfma_ks_tm launch of T > 1 token tiles on a K-split plan, on that state.  The counters keep an
+// epoch bit between launches and the slabs the last epoch's tagged words, both laid out by T: where
+// the state may hold another layout's (another T before, or a captured launch that replays at any
+// time) the region this T uses is zeroed on the stream ahead of the launch
+void launch_linear_tiles(gs_plan *p, int replica, linear_ks_state &l, const void *X, void *Y, uint32_t n, uint32_t T,
+                         hipStream_t s, const gsk::epilogue &e) {
+    const gs::device_plan &d = p->st.dev;
+    const size_t slab = (size_t)d.n_rows_aux * d.ksplit * d.maxr * 2048u, nctr = (size_t)d.n_rows_aux * T;
+    GS_CHECK(l.buf && T <= l.cap, "gs_linear: K-split state smaller than the launch");
+    uint32_t *arrivals = l.err - nctr;
+    const bool cap = capturing(s);
+    l.captured |= cap;
+    if (l.last != T || l.captured) {
+        GS_HIP(hipMemsetAsync(l.buf, 0, slab * T, s));
+        GS_HIP(hipMemsetAsync(arrivals, 0, nctr * sizeof(uint32_t), s));
+    }
+    l.last = 0;  // (unknown if the launch throws)
+    gs::launch_linear_fused(p->st, replica, X, Y, n, s, e, (float *)l.buf, arrivals);
+    l.last = T;
+}
 
 }  // namespace
 
@@ -878,7 +961,23 @@ int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, c
         }
         hipStream_t s = (hipStream_t)stream;
         if (linear_fused(p, N) && (uintptr_t)X % 16 == 0) {
-            gs::launch_linear_fused(p->st, replica, X, Y, N, s, e);
+            // k_mfma_ks_tm on 32-token tiles: one launch, or several in token order where the tiles'
+            // K-split state would pass LINEAR_WS_KB.  A launch of one tile (the plan's own width, a
+            // remainder) runs on the upload's state; the state of the others is there before the first
+            const std::vector<uint32_t> tiles = linear_tiles(p, N);
+            const uint32_t most = *std::max_element(tiles.begin(), tiles.end());
+            linear_ks_state *ks_state = p->st.dev.ksplit > 1 && most > 1 ? &ensure_linear_ks(p, replica, most, s) : nullptr;
+            uint32_t tok = 0;
+            for (uint32_t T : tiles) {
+                const uint32_t n = std::min(N - tok, T * 32u);
+                const void *x = (const char *)X + (size_t)tok * p->st.K * eb;
+                void *y = (char *)Y + (size_t)tok * p->st.M * eb;
+                gsk::epilogue et = e;  // (the bias is per output feature: not offset)
+                if (e.residual) et.residual = (const char *)e.residual + (size_t)tok * p->st.M * eb;
+                if (ks_state && T > 1) launch_linear_tiles(p, replica, *ks_state, x, y, n, T, s, et);
+                else gs::launch_linear_fused(p->st, replica, x, y, n, s, et);
+                tok += n;
+            }
             return;
         }
         // every other plan, width and alignment: X -> B (K x N), the plan's launches into C (M x N),
@@ -898,6 +997,33 @@ int gs_plan_linear_fused(gs_plan_t *p, int n_tokens) {
         fused = linear_fused(p, (uint32_t)n_tokens) ? 1 : 0;
     });
     return rc < 0 ? rc : fused;
+}
+
+int gs_plan_linear_launches(gs_plan_t *p, int n_tokens, int *tiles, int cap) {
+    int count = 0;
+    const int rc = guard([&] {
+        GS_CHECK(p && n_tokens >= 1 && cap >= 0 && (cap == 0 || tiles), "bad argument");
+        for (gs::plan_state *s : kernel_states(p)) GS_CHECK(s->uploaded, "plan is not on the device");
+        if (!linear_fused(p, (uint32_t)n_tokens)) return;
+        const std::vector<uint32_t> ls = linear_tiles(p, (uint32_t)n_tokens);
+        count = (int)ls.size();
+        for (int i = 0; i < count && i < cap; i++) tiles[i] = (int)ls[(size_t)i];
+    });
+    return rc < 0 ? rc : count;
+}
+
+int gs_linear_tile_split(uint64_t row_blocks, int k_ranges, int row_tiles, int n_tokens, long long ws_kb,
+                         unsigned long long *tile_bytes, int *tiles, int cap) {
+    int count = 0;
+    const int rc = guard([&] {
+        GS_CHECK(row_blocks >= 1 && k_ranges >= 1 && row_tiles >= 1 && n_tokens >= 1 && cap >= 0 && (cap == 0 || tiles), "bad argument");
+        if (tile_bytes) *tile_bytes = gs::ks_tm_tile_bytes(row_blocks, (uint32_t)k_ranges, (uint32_t)row_tiles);
+        const std::vector<uint32_t> ls = gs::ks_tm_tile_split(
+            (uint32_t)n_tokens, gs::ks_tm_tile_cap(row_blocks, (uint32_t)k_ranges, (uint32_t)row_tiles, ws_kb));
+        count = (int)ls.size();
+        for (int i = 0; i < count && i < cap; i++) tiles[i] = (int)ls[(size_t)i];
+    });
+    return rc < 0 ? rc : count;
 }
 
 int gs_spmm_rotate(gs_plan_t *p, int count, int first, const void *const *B_ptrs, void *const *C_ptrs, int n_ptrs,
@@ -1014,6 +1140,15 @@ int gs_plan_device_status(gs_plan_t *p, gs_stream_t stream) {
                 GS_HIP(hipMemset(w, 0, sizeof(v)));  // reported once
                 what += (what.empty() ? "" : ", ") + k->dev.kernel + " replica " + std::to_string(r);
             }
+        }
+        // ... and the word of gs_linear's launches of more than one token tile (linear_ks_state)
+        for (size_t r = 0; r < p->lin_ks.size(); r++) {
+            if (!p->lin_ks[r].buf) continue;
+            uint32_t v = 0;
+            GS_HIP(hipMemcpy(&v, p->lin_ks[r].err, sizeof(v), hipMemcpyDeviceToHost));
+            if (!v) continue;
+            GS_HIP(hipMemset(p->lin_ks[r].err, 0, sizeof(v)));
+            what += (what.empty() ? "" : ", ") + std::string("k_mfma_ks_tm replica ") + std::to_string(r);
         }
         if (!what.empty())
             throw gs::gs_error("K-split combine timed out waiting for a partial slab (" + what +

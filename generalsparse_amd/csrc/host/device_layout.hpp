@@ -8,6 +8,7 @@
 #include "code_generator.hpp"
 #include "../hip_code/kernel_consts.hpp"
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -100,6 +101,25 @@ inline bool ks_ct8_fits(uint32_t RT, uint32_t MAXG) { return (RT == 2 && MAXG <=
 // those that hold their registers (the kernel's resource table); other plans take the three-launch path
 constexpr bool ks_tm_fits(uint32_t RT, uint32_t MAXG) { return RT >= 2 && RT <= 8 && MAXG >= 1 && MAXG <= 4; }
 inline uint32_t ks_col_tiles_ct(uint32_t N, uint32_t CT) { return (N + 16 * CT - 1) / (16 * CT); }
+// k_mfma_ks_tm at any token count: T = ceil(n / 32) token tiles on a 1-D grid of nb * S * T workgroups
+// (nb row blocks, S K ranges, RT row tiles), T in 14 bits of the kernel's `prio` argument.
+// K-split state of one tile (S > 1): a 32-token fp32 slab per (row block, K range) -- 256 * RT * 2 floats
+// -- and an arrival counter per row block
+constexpr uint32_t kKsTmMaxTiles = 16383;
+inline uint64_t ks_tm_tile_bytes(uint64_t nb, uint32_t S, uint32_t RT) { return nb * S * RT * 2048u + nb * 4u; }
+// the most tiles one launch carries: the 14 bits, a grid below 2^31 workgroups and, with S > 1, the tiles
+// whose state fits ws_kb KB (LINEAR_WS_KB; at least 1: a single tile runs on the upload's own state)
+inline uint32_t ks_tm_tile_cap(uint64_t nb, uint32_t S, uint32_t RT, int64_t ws_kb) {
+    uint64_t cap = std::min<uint64_t>(kKsTmMaxTiles, 0x7fffffffull / std::max<uint64_t>(1, nb * S));
+    if (S > 1) cap = std::min<uint64_t>(cap, (uint64_t)std::max<int64_t>(0, ws_kb) * 1024u / ks_tm_tile_bytes(nb, S, RT));
+    return (uint32_t)std::max<uint64_t>(1, cap);
+}
+// the launches of an n-token call, in token order: tiles per launch, each at most `cap`
+inline std::vector<uint32_t> ks_tm_tile_split(uint32_t n_tokens, uint32_t cap) {
+    std::vector<uint32_t> out;
+    for (uint32_t left = (n_tokens + 31u) / 32u; left; left -= out.back()) out.push_back(std::min(left, cap));
+    return out;
+}
 
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,

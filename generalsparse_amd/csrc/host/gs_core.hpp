@@ -127,6 +127,9 @@ struct config_t {
                                  // store (one rounding), 0 the post-pass k_epilogue every other family takes (the A/B)
     int64_t LINEAR_FUSE = 1;     // gs_linear on a k_mfma_ks plan that k_mfma_ks_tm covers: 1 that kernel (one launch, one
                                  // rounding), 0 the three-launch path every other plan takes (the A/B, the tests)
+    int64_t LINEAR_WS_KB = 65536;  // gs_linear at more than one token tile on a K-split plan: the most KB of slabs and
+                                 // arrival counters per replica (a cap, not a tuned number); a call with more tiles
+                                 // runs as several launches (device_layout.hpp ks_tm_tile_cap / ks_tm_tile_split)
     int64_t KS_HEAD = 1;        // k_mfma_ks: the head steps (each wave's first kKsDepth k-steps) at fixed, padded
                                  // places, loaded without their records (when the padding costs <= 6% more groups)
     int64_t KS_PERSIST = 0;      // k_mfma_ks: persistent grid size pulling (row block, K range) units (experiments build)

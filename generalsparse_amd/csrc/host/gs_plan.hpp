@@ -172,12 +172,17 @@ void launch_gather(const plan_state &p, const device_arrays &a, const void *B, v
 void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
                const gsk::epilogue &epi = gsk::epilogue_identity());
 // ks_tm_launch.hip: k_mfma_ks_tm, a k_mfma_ks plan on token-major activations (gs_linear: Y = X * A^T,
-// X: n_tokens x K, Y: n_tokens x M).  linear_fuses: the plan, its upload layout and the width are ones
-// the kernel is built for (32-token tiles at the plan's own width, 8 waves, 16-bit positions, K % 8 == 0,
-// LINEAR_FUSE on); the launch needs X 16-byte aligned as well.  Allocates nothing
+// X: n_tokens x K, Y: n_tokens x M).  linear_fuses: the plan and its upload layout are ones the kernel
+// is built for (a plan of 17 .. 32 tokens -- 32-token tiles -- 8 waves, 16-bit positions, K % 8 == 0,
+// LINEAR_FUSE on), at any token count; the launch needs X 16-byte aligned as well.
+// launch_linear_fused: ONE launch of ceil(n_tokens / 32) token tiles (at most kKsTmMaxTiles).  With
+// K ranges and more than one tile the caller passes K-split state laid out for that tile count --
+// slabs: ks_tm_tile_bytes' slab part per tile; arrivals: nb counters per tile, the device error word
+// right behind them -- whose counters and slab tags are zero or left by a launch of the same tile
+// count; null: the replica's own (one tile, shared with k_mfma_ks).  Allocates nothing
 bool linear_fuses(const plan_state &p, uint32_t n_tokens);
 void launch_linear_fused(const plan_state &p, int replica, const void *X, void *Y, uint32_t n_tokens, hipStream_t s,
-                         const gsk::epilogue &epi);
+                         const gsk::epilogue &epi, float *slabs = nullptr, uint32_t *arrivals = nullptr);
 // device_plan.hip: the two ends of gs_linear's three-launch path (parts.hpp k_tm_in / k_tm_out)
 // B (K x N) = X^T (X: N x K)
 void launch_tm_in(const void *X, void *B, uint64_t K, uint32_t N, int dtype, hipStream_t stream);

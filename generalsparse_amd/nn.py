@@ -14,7 +14,11 @@ class SparseLinear(torch.nn.Module):
     """y = activation(x @ W.T + bias) [+ residual] with W held as a compiled, uploaded Plan
     (gs_linear: activations token-major, as torch holds them, no transposes around the SpMM).
     plan: an uploaded Plan of the (out, in) weight; bias: None or `out` values (kept as a float32
-    buffer on the plan's device); activation: None or "relu"."""
+    buffer on the plan's device); activation: None or "relu".
+    tokens is the width the plan's tiles are built for, not a batch size the layer is tied to: a
+    layer built with tokens=32 (a k_mfma_ks plan) runs the one kernel k_mfma_ks_tm at any token
+    count -- 8 tokens of a decode step, 100 of a prefill chunk -- on ceil(n / 32) token tiles, and a
+    token's output has the same bits in every such call (Plan.linear_fused, Plan.linear_launches)."""
 
     def __init__(self, plan, bias=None, activation=None):
         super().__init__()
@@ -34,7 +38,8 @@ class SparseLinear(torch.nn.Module):
                    device=0, upload=True):
         """the plan from the non-zeros of a pruned (out, in) weight: from_coo, run_pipeline at
         N = tokens, compile, upload (upload=False stops before the device: the plan can be inspected,
-        the module cannot run)"""
+        the module cannot run).  tokens: the tile width (17 .. 32 for the one-kernel path), whatever
+        token counts forward will see"""
         _check_activation(activation)
         _dtype_code(dtype)
         w = torch.as_tensor(weight).detach().to("cpu", torch.float32).numpy()

@@ -156,10 +156,17 @@ int gs_plan_epilogue_fused(gs_plan_t *p, int N);
  * epi may be NULL; bias is per column of Y (row of A); residual is n_tokens x M, no overlap with Y.
  * The layout a linear layer holds its activations in: with A the (out, in) weight this is
  * F.linear(X, A, bias), the epilogue's stages in gs_spmm_ex's order on the fp32 sums.
- * A k_mfma_ks plan at its own tile width of 17 .. 32 tokens (8 waves, 16-bit positions, no row padding),
- * K % 8 == 0 and X 16-byte aligned runs ONE kernel, k_mfma_ks_tm, on the plan as uploaded: X is read
- * and Y written in place, the epilogue is applied in the store (one rounding), nothing is allocated
- * (gs_plan_linear_fused = 1).  Every other plan, width and alignment runs three launches: X
+ * A k_mfma_ks plan built for 17 .. 32 tokens (8 waves, 16-bit positions, no row padding), K % 8 == 0
+ * and X 16-byte aligned runs ONE kernel, k_mfma_ks_tm, on the plan as uploaded, at ANY n_tokens >= 1:
+ * ceil(n_tokens / 32) token tiles in one launch, the last one partial; X is read and Y written in
+ * place, the epilogue is applied in the store (one rounding); row t of Y has the same bits whatever
+ * n_tokens is and wherever token t stands (gs_plan_linear_fused = 1).  One tile -- n_tokens <= 32 --
+ * allocates nothing.  More tiles on a plan with K ranges (ksplit > 1) need K-split state per tile,
+ * (row blocks) x (ksplit x row tiles x 2048 + 4) bytes: one buffer per plan replica, allocated by the
+ * first such call and grown for more tiles, synchronously as the scratch below (refused inside stream
+ * capture the first time, legal later; freed with the plan).  Config LINEAR_WS_KB (65536) caps that
+ * buffer: a call whose tiles need more runs as several launches of the kernel on the stream, in
+ * token order (gs_plan_linear_launches tells them).  Every other plan and alignment runs three launches: X
  * transposed into a scratch B, the plan's gs_spmm_replica launches, and the epilogue with the
  * transpose back (at GS_F16 / GS_BF16 two roundings, as gs_spmm_ex's pass).  The scratch of (K + M) x
  * n_tokens elements belongs to the plan replica; it is allocated by the first call at a token count
@@ -172,6 +179,16 @@ int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, c
 /* 1: gs_linear at n_tokens runs k_mfma_ks_tm (given an aligned X), 0: the three-launch path (also for a
  * plan that is not on the device), < 0: error */
 int gs_plan_linear_fused(gs_plan_t *p, int n_tokens);
+/* how gs_linear would enqueue n_tokens (given an aligned X): returns the number of k_mfma_ks_tm
+ * launches and the token tiles (of 32) each carries in tiles[0 .. min(count, cap)), in token order;
+ * 0: the three-launch path; < 0: a bad argument or a plan that is not on the device.  Allocates nothing. */
+int gs_plan_linear_launches(gs_plan_t *p, int n_tokens, int *tiles, int cap);
+/* the arithmetic behind it, host only: a plan of row_blocks row blocks of row_tiles 16-row tiles over
+ * k_ranges K ranges, LINEAR_WS_KB = ws_kb.  *tile_bytes (may be NULL) gets the K-split state of one
+ * token tile; the return value and tiles[] are gs_plan_linear_launches' for such a plan (k_ranges = 1
+ * needs no state: only the limit of 16383 tiles per launch splits a call) */
+int gs_linear_tile_split(uint64_t row_blocks, int k_ranges, int row_tiles, int n_tokens, long long ws_kb,
+                         unsigned long long *tile_bytes, int *tiles, int cap);
 /* `count` SpMMs enqueued back to back from native code, call i using replica
  * (first + i) % replicas with B_ptrs / C_ptrs entry (first + i) % n_ptrs
  * (bench rotation without a host round trip per launch) */
