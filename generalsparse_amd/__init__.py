@@ -20,10 +20,10 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import GS_BF16, GS_F16, GS_F32, GsError
+from ._lib import GS_BF16, GS_F16, GS_F32, GS_W_FP8_E4M3, GS_W_NATIVE, GsError
 
 __all__ = ["Plan", "Batch", "Rotation", "SparseLinear", "set_config", "GsError", "GS_F16", "GS_F32", "GS_BF16", "PIPELINES", "load_library",
-           "convert_values"]
+           "convert_values", "GS_W_NATIVE", "GS_W_FP8_E4M3", "fp8_quantize", "fp8_decode"]
 
 # token_test.cc pipelines (+ the two compositions this engine adds)
 PIPELINES = ("thread_total", "warp_total", "block_total", "thread_bit_map", "warp_segment",
@@ -78,6 +78,49 @@ def convert_values(values, dtype):
     out = np.empty(x.size, np.float32 if code == GS_F32 else np.uint16)
     _lib.check(L.gs_convert_values(x.ctypes.data_as(_lib.f32p), x.size, code, ctypes.c_void_p(out.ctypes.data)))
     return out
+
+
+def _weights_code(weights):
+    if weights in (None, GS_W_NATIVE, "native"):
+        return GS_W_NATIVE
+    if weights in (GS_W_FP8_E4M3, "fp8", "fp8_e4m3", "e4m3"):
+        return GS_W_FP8_E4M3
+    raise ValueError(f"unsupported weights {weights!r} (None or \"fp8\")")
+
+
+def fp8_quantize(val, row, n_rows, row_scale=None):
+    """A's values as Plan.upload(weights="fp8") stores them (gs_quantize_fp8_rows): (codes, scale) with
+    codes[i] = e4m3fn(val[i] / scale[row[i]]) as uint8 -- an IEEE float32 division, rounded to nearest even
+    and saturated at +-448 (never a NaN code) -- and scale the n_rows float32 scales used: row_scale, or
+    by default 2^e with the smallest e such that max|val of the row| / 2^e <= 448 (1 for a row without
+    values).  Refused (GsError): a non-finite value, a row >= n_rows, a scale that is not finite and > 0,
+    a row_scale of another length."""
+    L = _lib.load()
+    v = np.ascontiguousarray(val, dtype=np.float32).ravel()
+    r = np.asarray(row).ravel()
+    if r.size != v.size:
+        raise _refused("fp8_quantize: val and row lengths differ")
+    if r.size and (not np.issubdtype(r.dtype, np.integer) or r.min() < 0):
+        raise _refused("fp8_quantize: row must hold non-negative integers")
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    sp, ns = None, 0
+    if row_scale is not None:
+        row_scale = np.ascontiguousarray(row_scale, dtype=np.float32).ravel()
+        sp, ns = row_scale.ctypes.data_as(_lib.f32p), row_scale.size
+    codes = np.zeros(v.size, np.uint8)
+    scale = np.zeros(int(n_rows), np.float32)
+    _lib.check(L.gs_quantize_fp8_rows(v.ctypes.data_as(_lib.f32p), r.ctypes.data_as(_lib.u64p), v.size, int(n_rows), sp, ns,
+                                      codes.ctypes.data_as(_lib.u8p), scale.ctypes.data_as(_lib.f32p)))
+    return codes, scale
+
+
+def fp8_decode(codes):
+    """OCP e4m3fn codes (uint8) as float32, exactly (gs_fp8_decode); 0x7f / 0xff give NaN"""
+    L = _lib.load()
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    out = np.zeros(c.size, np.float32)
+    _lib.check(L.gs_fp8_decode(c.ravel().ctypes.data_as(_lib.u8p), c.size, out.ctypes.data_as(_lib.f32p)))
+    return out.reshape(c.shape)
 
 
 def _torch_dtype(code):
@@ -370,10 +413,49 @@ class Plan:
         return buf.value.decode()
 
     # --------------------------------------------------------------- device
-    def upload(self, dtype="f16", device=0):
+    def upload(self, dtype="f16", device=0, *, weights=None, row_scale=None):
+        """A's arrays to the device in the layout of the plan's kernel; B and C of every later call hold
+        `dtype`.  weights="fp8" (gs_plan_upload_ex, GS_W_FP8_E4M3) stores A's values as OCP e4m3fn codes
+        with one float32 scale per row -- row_scale (M values, finite and > 0) or, by default, the power
+        of two that brings the row's largest magnitude into (224, 448]: 3 instead of 4 bytes per stored
+        entry.  Only for an undivided k_mfma_ks plan built for 17 .. 32 columns, dtype "f16", K a
+        multiple of 8; anything else is refused and the plan is then not on the device.  Such a plan runs
+        spmm at the width it was built for and linear at any token count; with power-of-two scales the
+        results are bit for bit those of an f16 plan of fp8_decode(codes) * scale[row]."""
         self.dtype_code = _dtype_code(dtype)
-        _lib.check(self._L.gs_plan_upload(self._h, self.dtype_code, int(device)))
+        w = _weights_code(weights)
+        if w == GS_W_NATIVE:
+            if row_scale is not None:
+                raise _refused("upload: row_scale goes with weights=\"fp8\"")
+            _lib.check(self._L.gs_plan_upload(self._h, self.dtype_code, int(device)))
+            return self
+        sp = None
+        if row_scale is not None:
+            row_scale = np.ascontiguousarray(row_scale, dtype=np.float32).ravel()
+            rows = self.info()["rows"]
+            if row_scale.size != rows:
+                raise _refused(f"upload: row_scale must hold one scale per row of A ({rows}), not {row_scale.size}")
+            sp = row_scale.ctypes.data_as(_lib.f32p)
+        _lib.check(self._L.gs_plan_upload_ex(self._h, self.dtype_code, w, sp, int(device)))
         return self
+
+    def fp8_layout(self, row_scale=None):
+        """(codes, scale): the 8-bit value array -- 8 e4m3 codes per entry group of the plan's k_mfma_ks
+        layout, pad slots 0 -- and the M scales exactly as upload(weights="fp8", row_scale=row_scale)
+        would lay them out under the current config; no device is touched (gs_plan_fp8_layout)"""
+        sp = None
+        if row_scale is not None:
+            row_scale = np.ascontiguousarray(row_scale, dtype=np.float32).ravel()
+            if row_scale.size != self.info()["rows"]:
+                raise _refused("fp8_layout: row_scale must hold one scale per row of A")
+            sp = row_scale.ctypes.data_as(_lib.f32p)
+        n = ctypes.c_uint64(0)
+        _lib.check(self._L.gs_plan_fp8_layout(self._h, sp, None, 0, ctypes.byref(n), None))
+        codes = np.zeros(n.value, np.uint8)
+        scale = np.zeros(self.info()["rows"], np.float32)
+        _lib.check(self._L.gs_plan_fp8_layout(self._h, sp, codes.ctypes.data_as(_lib.u8p), codes.size, ctypes.byref(n),
+                                              scale.ctypes.data_as(_lib.f32p)))
+        return codes, scale
 
     def add_replica(self):
         _lib.check(self._L.gs_plan_add_replica(self._h))

@@ -12,7 +12,10 @@ LIB_PATH = os.environ.get("GS_LIBRARY") or os.path.join(PKG_DIR, "libgeneralspar
 GS_F32 = 0
 GS_F16 = 1
 GS_BF16 = 2
+GS_W_NATIVE = 0  # A's values in the plan's dtype
+GS_W_FP8_E4M3 = 1  # ... as OCP e4m3fn codes with one fp32 scale per row (gs_plan_upload_ex)
 
+u8p = ctypes.POINTER(ctypes.c_uint8)
 u64p = ctypes.POINTER(ctypes.c_uint64)
 f32p = ctypes.POINTER(ctypes.c_float)
 f64p = ctypes.POINTER(ctypes.c_double)
@@ -35,7 +38,7 @@ class GsPlanInfo(ctypes.Structure):
                 ("n_kernels", ctypes.c_int), ("device_kernel", ctypes.c_char * 32),
                 ("index_formulas", ctypes.c_int), ("index_bytes_saved", ctypes.c_uint64),
                 ("ks_nt", ctypes.c_uint32), ("ks_head_groups", ctypes.c_uint32),
-                ("nm_tiles", ctypes.c_uint32), ("ks_wpos", ctypes.c_uint32)]
+                ("nm_tiles", ctypes.c_uint32), ("ks_wpos", ctypes.c_uint32), ("weights", ctypes.c_uint32)]
 
 
 class GsEpilogue(ctypes.Structure):
@@ -82,6 +85,10 @@ SIGNATURES = {
                                  ctypes.c_int),
     "gs_plan_upload": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "gs_convert_values": ([f32p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "gs_plan_upload_ex": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int, f32p, ctypes.c_int], ctypes.c_int),
+    "gs_quantize_fp8_rows": ([f32p, u64p, ctypes.c_uint64, ctypes.c_uint64, f32p, ctypes.c_uint64, u8p, f32p], ctypes.c_int),
+    "gs_fp8_decode": ([u8p, ctypes.c_uint64, f32p], ctypes.c_int),
+    "gs_plan_fp8_layout": ([ctypes.c_void_p, f32p, u8p, ctypes.c_uint64, u64p, f32p], ctypes.c_int),
     "gs_plan_add_replica": ([ctypes.c_void_p], ctypes.c_int),
     "gs_spmm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "gs_spmm_replica": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,

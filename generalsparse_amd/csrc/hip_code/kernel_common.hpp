@@ -204,6 +204,56 @@ __device__ __forceinline__ uint32_t b_piece(uint32_t k, uint32_t p) {
     return p ^ (sw & (uint32_t)(CT - 1));
 }
 
+// FP8 weights (k_mfma_ks_w8, k_mfma_ks_tm with VB = 8): a group's 8 OCP e4m3fn codes (byte e = entry e) as the 4
+// registers of packed fp16 the 16-bit form loads (halfword e = entry e).  Exact: every finite e4m3 value
+// is an fp16 value.  v_cvt_scalef32_pk_f16_fp8 with scale 1.0 converts two codes per instruction (the low
+// or the high pair of a register: op_sel), 4 VALU per group.
+// GS_KS_W8_ALU (0; 1 in a variant build for the A/B): the same values by integer operations and one
+// packed multiply -- the two codes into the high byte of each half (v_perm_b32), sign | (exponent,
+// mantissa) >> 1 as the fp16 bits of value / 256, times 256 (v_pk_mul_f16; fp16 denormals on)
+#ifndef GS_KS_W8_ALU
+#define GS_KS_W8_ALU 0
+#endif
+__device__ __forceinline__ u32x4 ks_decode8(const u32x2 &c) {
+    u32x4 o;
+#if GS_KS_W8_ALU
+    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+    const h2v k256 = {(_Float16)256.f, (_Float16)256.f};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t w = __builtin_amdgcn_perm(0u, c[i >> 1], (i & 1) ? 0x030c020cu : 0x010c000cu);
+        const uint32_t b = (w & 0x80008000u) | ((w & 0x7f007f00u) >> 1);
+        h2v h;
+        __builtin_memcpy(&h, &b, 4);
+        h = h * k256;
+        uint32_t r;
+        __builtin_memcpy(&r, &h, 4);
+        o[i] = r;
+    }
+#else
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const auto h = (i & 1) ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[i >> 1], 1.0f, true)
+                               : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[i >> 1], 1.0f, false);
+        uint32_t r;
+        __builtin_memcpy(&r, &h, 4);
+        o[i] = r;
+    }
+#endif
+    return o;
+}
+// a loaded group's 8 values as 16-bit words: the registers themselves (VB = 16), or the decoded codes
+template <int VB>
+__device__ __forceinline__ const u32x4 &ks_group_values(const u32x4 &v) {
+    static_assert(VB == 16, "16-bit values are loaded as u32x4");
+    return v;
+}
+template <int VB>
+__device__ __forceinline__ u32x4 ks_group_values(const u32x2 &c) {
+    static_assert(VB == 8, "e4m3 codes are loaded as u32x2");
+    return ks_decode8(c);
+}
+
 // K-split combine: the last ticket holder's read of 4 words of another workgroup's slab
 // (each word tagged in its low mantissa bit): agent-scope (sc1) loads until every tag reads
 // `tag`.  The writer holds an earlier ticket, so it is resident and its stores are issued or

@@ -1,6 +1,7 @@
 // hip_code/mfma_ks.hpp -- k_mfma_ks: BMTB row blocks on the matrix cores with K split over
 // workgroups; k_mfma_ks_group (several launches as one grid) and, in the experiments build,
-// k_mfma_ks_persist.  Instantiated by kernels/ks_launch.hip.
+// k_mfma_ks_persist.  Instantiated by kernels/ks_launch.hip; k_mfma_ks_w8 (FP8 weights) by
+// kernels/ks_w8_launch.hip.
 #pragma once
 
 #include "kernel_common.hpp"
@@ -79,15 +80,25 @@ __device__ constexpr int vmcnt_imm() {
 #define GS_KS_SLOT_ORDER 1
 #endif
 enum : int { kKsPosU16 = 0, kKsPos8 = 1, kKsPosWin = 2 };
-template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, int PF = kKsPosU16, int NTL = 0, class ET = f16>
+// VB, the storage of A's values: 16 (8 x 16-bit ET words per group: tV as u32x4) or 8 (FP8 weights, fp16
+// activations: tV holds 8 bytes per group, one OCP e4m3fn code per entry, read as u32x2 through the same
+// ld_once_if choice).  ks_decode8 turns a group's 8 codes into the 4 registers of packed fp16 the 16-bit
+// form loads -- every finite e4m3 value is an fp16 value, so the scatter, the fragments and the MFMAs are
+// the 16-bit form's on the same numbers -- and store_item multiplies the fp32 sum of a row by w_scale[row]
+// (__fmul_rn, before epilogue_apply: at S == 1 and in the last ticket holder's combine; the slabs keep
+// unscaled partial sums).  w_scale is indexed as the epilogue's bias is.  ks_decode8: kernel_common.hpp
+template <int CT, int RT, int W, int D, int MAXG, bool STAMPS, bool AP = true, int PF = kKsPosU16, int NTL = 0, class ET = f16,
+          int VB = 16>
 __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_row, const u32x4 *__restrict__ tP,
                                         const u32x4 *__restrict__ tV, const u32x2 *__restrict__ steps,
                                         const ET *__restrict__ B, ET *__restrict__ C, uint32_t K, uint32_t N, uint32_t S,
                                         uint32_t NS, uint32_t nwg, uint32_t row_base, float *__restrict__ slabs,
                                         uint32_t *__restrict__ arrivals, uint64_t *__restrict__ stamps, uint32_t bx,
                                         uint32_t prio, const uint8_t *__restrict__ tW = nullptr,
-                                        const epilogue &epi = epilogue_identity()) {
+                                        const epilogue &epi = epilogue_identity(),
+                                        const float *__restrict__ w_scale = nullptr) {
     constexpr bool P8 = PF == kKsPos8, WP = PF == kKsPosWin;
+    static_assert(VB == 16 || (VB == 8 && std::is_same<ET, f16>::value), "FP8 weights decode to fp16");
     constexpr uint32_t RB = 32 * CT;  // bytes per LDS B row (a 16*CT-column tile)
     constexpr uint32_t UB = 2 * CT;   // 16-B units per B row
     constexpr uint32_t IMG = ks_image_bytes<RT>();
@@ -117,8 +128,11 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     const size_t ubase = (size_t)u * NS;
     using PV = typename std::conditional<P8 || WP, u32x2, u32x4>::type;
     const PV *tPp = reinterpret_cast<const PV *>(tP);
+    using VV = typename std::conditional<VB == 8, u32x2, u32x4>::type;  // a group's values as loaded
+    const VV *tVp = reinterpret_cast<const VV *>(tV);
     PV P[D][MAXG];
-    u32x4 V[D][MAXG], BR[D][CT];
+    VV V[D][MAXG];
+    u32x4 BR[D][CT];
     uint32_t WN[D][MAXG];  // WP: the groups' window bytes
     u32x2 NX[D];      // per slot: record of the step the slot loads next
     uint32_t CN[D];   // per slot: group count of the step whose groups it holds
@@ -161,7 +175,7 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
     };
     // the groups of step i (b0: first group, gc: count), then the record of step i + D
     auto load_g_at = [&](uint32_t i, uint32_t b0, uint32_t gc, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG],
-                         u32x4 (&V_)[MAXG], uint32_t (&W_)[MAXG]) {
+                         VV (&V_)[MAXG], uint32_t (&W_)[MAXG]) {
         CN_ = gc;
         NX_ = rec_of(i + D);
 #pragma unroll
@@ -169,11 +183,11 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
             const uint32_t qg = lane + 64u * j;
             const size_t at = (size_t)b0 + (qg < gc ? qg : 0u);
             P_[j] = ld_once_if<(NTL & 1) != 0>(tPp + at);
-            V_[j] = ld_once_if<(NTL & 1) != 0>(tV + at);
+            V_[j] = ld_once_if<(NTL & 1) != 0>(tVp + at);
             if constexpr (WP) W_[j] = ld_once_if<(NTL & 1) != 0>(tW + at);
         }
     };
-    auto load_g = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG], uint32_t (&W_)[MAXG]) {
+    auto load_g = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], VV (&V_)[MAXG], uint32_t (&W_)[MAXG]) {
         load_g_at(i, __builtin_amdgcn_readfirstlane(NX_[0]), __builtin_amdgcn_readfirstlane(NX_[1]), NX_, CN_, P_, V_, W_);
     };
     // head steps (device_layout.cc ks_tiles::GH, prio bits 8..17): the first D steps of every wave
@@ -256,7 +270,7 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
             return 0u;
         }
     };
-    auto step = [&](auto fast, uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], u32x4 (&V_)[MAXG], u32x4 (&B_)[CT],
+    auto step = [&](auto fast, uint32_t i, u32x2 &NX_, uint32_t &CN_, PV (&P_)[MAXG], VV (&V_)[MAXG], u32x4 (&B_)[CT],
                     uint32_t (&W_)[MAXG]) {
         const bool live = i < nsw;  // wave-uniform
         const uint32_t gc = CN_;
@@ -288,9 +302,10 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
             for (int j = 0; j < MAXG; j++) {
                 if (lane + 64u * j < gc) {
                     const uint32_t hb = grp_hb(P_[j]);
+                    const auto &gv = ks_group_values<VB>(V_[j]);  // the group's 8 values as 16-bit words
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
-                        const uint16_t v = (uint16_t)((V_[j][e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                        const uint16_t v = (uint16_t)((gv[e >> 1] >> (16 * (e & 1))) & 0xffffu);
                         if constexpr (WP) {
                             *reinterpret_cast<uint16_t *>(wa[j][e]) = v;
                         } else {
@@ -432,6 +447,20 @@ __device__ __forceinline__ void ks_body(const uint32_t *__restrict__ bmtb_first_
         const uint32_t ln = t & 63u, tt = t >> 6, rt = tt / CT, ct = tt % CT;
         const uint32_t col = 16u * ct + (ln & 15u), rb = 16u * rt + 4u * (ln >> 4);
         if (col >= nv) return;
+        if constexpr (VB == 8) {  // FP8 weights: the row's scale on the fp32 sum first, then as below
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++)
+                if (rb + i < R) {
+                    const size_t row = (size_t)(row_base + r0 + rb + i), at = row * N + col0 + col;
+                    float o = __fmul_rn(w_scale[row], v[i]);
+                    if (fused) {
+                        const float res = epi.residual ? (float)static_cast<const ET *>(epi.residual)[at] : 0.f;
+                        o = epilogue_apply(epi, o, row, res);
+                    }
+                    C[at] = (ET)o;
+                }
+            return;
+        }
         if (fused) {  // the launch's epilogue on the fp32 sum, rounded once (epilogue_apply)
 #pragma unroll
             for (uint32_t i = 0; i < 4; i++)
@@ -524,6 +553,24 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks(const uint32_t *__restrict__
     // nwg == gridDim.x (an argument: kernarg preload)
     ks_body<CT, RT, W, D, MAXG, STAMPS, AP, PF, NTL, ET>(bmtb_first_row, tP, tV, steps, B, C, K, N, S, NS, nwg, row_base, slabs,
                                                     arrivals, stamps, blockIdx.x, prio, tW, epi);
+}
+
+// k_mfma_ks_w8 -- k_mfma_ks on a plan uploaded with FP8 weights (ks_body's VB = 8): the release layout
+// (fp16 activations, the apart layout, 16-bit positions, no stamps) and one more argument, the rows'
+// scales.  A kernel of its own name: the value storage and the scale pointer reach these instantiations
+// only, and every k_mfma_ks instantiation keeps its template arguments, its parameters and its symbol
+template <int CT, int RT, int W, int D, int MAXG, int NTL = 0>
+__global__ __launch_bounds__(64 * W) void k_mfma_ks_w8(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
+                                                       const u32x4 *__restrict__ tP,  // 8 x u16 position per group
+                                                       const u32x2 *__restrict__ tV,  // 8 x e4m3 code per group
+                                                       const u32x2 *__restrict__ steps, const f16 *__restrict__ B,
+                                                       f16 *__restrict__ C, uint32_t K, uint32_t N, uint32_t S, uint32_t NS,
+                                                       uint32_t nwg, uint32_t row_base, float *__restrict__ slabs,
+                                                       uint32_t *__restrict__ arrivals, uint32_t prio, epilogue epi,
+                                                       const float *__restrict__ w_scale) {  // one per row of A
+    ks_body<CT, RT, W, D, MAXG, false, true, kKsPosU16, NTL, f16, 8>(bmtb_first_row, tP, reinterpret_cast<const u32x4 *>(tV), steps,
+                                                                    B, C, K, N, S, NS, nwg, row_base, slabs, arrivals, nullptr,
+                                                                    blockIdx.x, prio, nullptr, epi, w_scale);
 }
 
 #ifdef GS_EXPERIMENTS

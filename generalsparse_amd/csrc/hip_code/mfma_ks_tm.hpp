@@ -1,5 +1,6 @@
 // hip_code/mfma_ks_tm.hpp -- k_mfma_ks_tm: k_mfma_ks with token-major activations, Y = X * A^T
-// (gs_linear).  Instantiated by kernels/ks_tm_launch.hip.
+// (gs_linear).  Instantiated by kernels/ks_tm_launch.hip; with FP8 weights (VB = 8) by
+// kernels/ks_tm_w8_launch.hip.
 #pragma once
 
 #include "kernel_common.hpp"
@@ -38,16 +39,27 @@ namespace gsk {
 //   2-byte stores otherwise.  epilogue_apply on the fp32 sum as in ks_body's store_item: bias[row] is
 //   per output feature, the residual is read token-major at Y's index; one rounding.
 // LDS: the W images, then the W partial tiles (kernel_consts.hpp ks_tm_lds_bytes).
+// VB is ks_body's (mfma_ks.hpp): 16, or 8 for a plan uploaded with FP8 weights (fp16 activations) -- tV
+// holds 8 e4m3 codes per group, decoded by ks_decode8 into the registers the scatter reads, and
+// store_item multiplies the fp32 sum of a row by its scale before the epilogue; everything else, the
+// K-split state included, is the 16-bit form's.  WS: the instantiations with VB = 8 -- and only they --
+// take one more argument, `const float *` scales, one per row of A (indexed as the bias is); the body
+// stays in the kernel (moved into a function, the 16-bit instantiations allocate registers differently)
 // ---------------------------------------------------------------------------
-template <int RT, int W, int D, int MAXG, int NTL = 0, class ET = f16>
+__device__ __forceinline__ const float *ks_scale_arg() { return nullptr; }
+__device__ __forceinline__ const float *ks_scale_arg(const float *p) { return p; }
+template <int RT, int W, int D, int MAXG, int NTL = 0, class ET = f16, int VB = 16, class... WS>
 __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restrict__ bmtb_first_row,  // nb+1
                                                        const u32x4 *__restrict__ tP,  // 8 x u16 position per group
-                                                       const u32x4 *__restrict__ tV,  // 8 x 16-bit value (ET) per group
+                                                       const u32x4 *__restrict__ tV,  // 8 x 16-bit value (ET) per group; VB = 8: 8 bytes
                                                        const u32x2 *__restrict__ steps,  // per (unit, k-step): first group, count
                                                        const ET *__restrict__ X, ET *__restrict__ Y, uint32_t K,
                                                        uint32_t N, uint32_t M, uint32_t S, uint32_t NS, uint32_t nwg,
                                                        uint32_t row_base, float *__restrict__ slabs,
-                                                       uint32_t *__restrict__ arrivals, uint32_t prio, epilogue epi) {
+                                                       uint32_t *__restrict__ arrivals, uint32_t prio, epilogue epi,
+                                                       WS... w_scale_arg) {
+    static_assert(VB == 16 ? sizeof...(WS) == 0 : (VB == 8 && sizeof...(WS) == 1 && std::is_same<ET, f16>::value),
+                  "16-bit values, or FP8 weights (fp16 activations) with the rows' scales as the last argument");
     constexpr int CT = 2;
     constexpr uint32_t IMG = ks_image_bytes<RT>();
     static_assert(!ks_red_halves(CT, RT, W), "the W partial tiles fit LDS");
@@ -79,7 +91,10 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     // ---- this wave's k-steps w, w+W, ... (records, groups and head steps as in ks_body)
     const uint32_t nsw = NS > wv ? (NS - wv + W - 1u) / W : 0u;
     const size_t ubase = (size_t)u * NS;
-    u32x4 P[D][MAXG], V[D][MAXG], BR[D][CT];
+    using VV = typename std::conditional<VB == 8, u32x2, u32x4>::type;  // a group's values as loaded
+    const VV *tVp = reinterpret_cast<const VV *>(tV);
+    u32x4 P[D][MAXG], BR[D][CT];
+    VV V[D][MAXG];
     u32x2 NX[D];     // per slot: record of the step the slot loads next
     uint32_t CN[D];  // per slot: group count of the step whose groups it holds
     uint32_t vz;
@@ -118,7 +133,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     };
     // the groups of step i (b0: first group, gc: count), then the record of step i + D
     auto load_g_at = [&](uint32_t i, uint32_t b0, uint32_t gc, u32x2 &NX_, uint32_t &CN_, u32x4 (&P_)[MAXG],
-                         u32x4 (&V_)[MAXG]) {
+                         VV (&V_)[MAXG]) {
         CN_ = gc;
         NX_ = rec_of(i + D);
 #pragma unroll
@@ -126,10 +141,10 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
             const uint32_t qg = lane + 64u * j;
             const size_t at = (size_t)b0 + (qg < gc ? qg : 0u);
             P_[j] = ld_once_if<(NTL & 1) != 0>(tP + at);
-            V_[j] = ld_once_if<(NTL & 1) != 0>(tV + at);
+            V_[j] = ld_once_if<(NTL & 1) != 0>(tVp + at);
         }
     };
-    auto load_g = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, u32x4 (&P_)[MAXG], u32x4 (&V_)[MAXG]) {
+    auto load_g = [&](uint32_t i, u32x2 &NX_, uint32_t &CN_, u32x4 (&P_)[MAXG], VV (&V_)[MAXG]) {
         load_g_at(i, __builtin_amdgcn_readfirstlane(NX_[0]), __builtin_amdgcn_readfirstlane(NX_[1]), NX_, CN_, P_, V_);
     };
     // the prologue issues slot by slot in the step loop's own order (ks_body, GS_KS_SLOT_ORDER)
@@ -172,7 +187,7 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
     // step i on its set, then the set is reloaded with step i + D (issued whether or not step i
     // exists: every loop iteration issues the same loads)
     auto ent_h = [&](const u32x4 &p, int e) -> uint32_t { return (p[e >> 1] >> (16 * (e & 1))) & 0xffffu; };
-    auto step = [&](auto fast, uint32_t i, u32x2 &NX_, uint32_t &CN_, u32x4 (&P_)[MAXG], u32x4 (&V_)[MAXG], u32x4 (&B_)[CT]) {
+    auto step = [&](auto fast, uint32_t i, u32x2 &NX_, uint32_t &CN_, u32x4 (&P_)[MAXG], VV (&V_)[MAXG], u32x4 (&B_)[CT]) {
         const bool live = i < nsw;  // wave-uniform
         const uint32_t gc = CN_;
         typedef typename mfma_elem<ET>::frag frag;
@@ -182,9 +197,10 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
 #pragma unroll
             for (int j = 0; j < MAXG; j++) {
                 if (lane + 64u * j < gc) {
+                    const auto &gv = ks_group_values<VB>(V_[j]);  // the group's 8 values as 16-bit words
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
-                        const uint16_t v = (uint16_t)((V_[j][e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                        const uint16_t v = (uint16_t)((gv[e >> 1] >> (16 * (e & 1))) & 0xffffu);
                         *reinterpret_cast<uint16_t *>(img + ent_h(P_[j], e) * 2u) = v;
                     }
                 }
@@ -280,6 +296,9 @@ __global__ __launch_bounds__(64 * W) void k_mfma_ks_tm(const uint32_t *__restric
 #pragma unroll
         for (uint32_t i = 0; i < 4; i++) {
             float o = v[i];
+            if constexpr (VB == 8) {  // FP8 weights: the row's scale on the fp32 sum, before the epilogue
+                if (rb + i < R) o = __fmul_rn(ks_scale_arg(w_scale_arg...)[row + i], o);
+            }
             if (fused && rb + i < R) {  // the launch's epilogue on the fp32 sum, rounded once (epilogue_apply)
                 const float res = epi.residual ? (float)static_cast<const ET *>(epi.residual)[at + i] : 0.f;
                 o = epilogue_apply(epi, o, row + i, res);

@@ -862,11 +862,15 @@ int gs_plan_generate_program(gs_plan_t *p, const char *root_dir, int repeat, cha
     });
 }
 
-int gs_plan_upload(gs_plan_t *p, int dtype, int device) {
+int gs_plan_upload(gs_plan_t *p, int dtype, int device) { return gs_plan_upload_ex(p, dtype, GS_W_NATIVE, nullptr, device); }
+
+int gs_plan_upload_ex(gs_plan_t *p, int dtype, int weights, const float *row_scale, int device) {
     return guard([&] {
         GS_CHECK(p, "null plan");
         auto ks = kernel_states(p);
-        for (gs::plan_state *s : ks) gs::upload_plan(*s, dtype, device);
+        GS_CHECK(weights == GS_W_NATIVE || weights == GS_W_FP8_E4M3, "weights must be GS_W_NATIVE or GS_W_FP8_E4M3");
+        GS_CHECK(weights == GS_W_NATIVE || !divided(p), "FP8 weights: an undivided plan only (this one is divided into sub-matrices)");
+        for (gs::plan_state *s : ks) gs::upload_plan(*s, dtype, device, weights, row_scale);
         // parent-indexed sub-matrices, grouped by the row range they refer to
         free_groups(p);
         free_linear(p);  // (the dtype or the device may have changed)
@@ -908,6 +912,42 @@ int gs_convert_values(const float *in, uint64_t n, int dtype, void *out) {
     return guard([&] {
         GS_CHECK(n == 0 || (in && out), "null argument");
         gs::convert_values(in, n, dtype, out);
+    });
+}
+
+int gs_quantize_fp8_rows(const float *val, const uint64_t *row, uint64_t n, uint64_t n_rows, const float *row_scale,
+                         uint64_t n_scale, uint8_t *codes, float *scale) {
+    return guard([&] {
+        GS_CHECK((n == 0 || (val && row && codes)) && (n_rows == 0 || scale), "null argument");
+        GS_CHECK(!row_scale || n_scale == n_rows,
+                 "row_scale must hold one scale per row (" + std::to_string(n_rows) + "), not " + std::to_string(n_scale));
+        gs::quantize_fp8_rows(val, row, n, n_rows, row_scale, codes, scale);
+    });
+}
+
+int gs_fp8_decode(const uint8_t *codes, uint64_t n, float *out) {
+    return guard([&] {
+        GS_CHECK(n == 0 || (codes && out), "null argument");
+        for (uint64_t i = 0; i < n; i++) out[i] = gs::e4m3_bits_to_f32(codes[i]);
+    });
+}
+
+int gs_plan_fp8_layout(gs_plan_t *p, const float *row_scale, uint8_t *codes, uint64_t cap, uint64_t *n_codes, float *scale) {
+    return guard([&] {
+        GS_CHECK(p && n_codes && (cap == 0 || codes), "null argument");
+        GS_CHECK(!divided(p), "FP8 weights: an undivided plan only (this one is divided into sub-matrices)");
+        gs::plan_state &s = p->st;
+        GS_CHECK(s.cg && s.cg->is_compiled(), "plan must be compiled first");
+        const int sb = s.cg->get_sub_matrix_id();
+        GS_CHECK(gs::row_num_of_sub_matrix(*s.meta, sb) == s.M, "FP8 weights: a plan without padded rows only");
+        const gs::fp8_request w8{row_scale};
+        const gs::mc_layout mc = gs::choose_matrix_core_layout(*s.meta, s.cg->get_kernel_spec(), sb, s.K, gs::kF16, &w8);
+        gs::check_fp8_layout(mc, s.K);
+        *n_codes = mc.ks.val8.size();
+        if (cap >= mc.ks.val8.size()) {
+            std::memcpy(codes, mc.ks.val8.data(), mc.ks.val8.size());
+            if (scale) std::memcpy(scale, mc.w8_scale.data(), mc.w8_scale.size() * sizeof(float));
+        }
     });
 }
 
@@ -982,6 +1022,10 @@ int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, c
         }
         // every other plan, width and alignment: X -> B (K x N), the plan's launches into C (M x N),
         // the epilogue and the way back in k_tm_out
+        // (FP8 weights: the SpMM in the middle runs at the plan's width only -- refused before any launch)
+        GS_CHECK(p->st.dev.weights != gs::kWFp8 || N == p->st.dev.lds_N,
+                 "gs_linear: a plan with FP8 weights takes the three-launch path (misaligned x, LINEAR_FUSE = 0) at the "
+                 "token count it was built for (" + std::to_string(p->st.dev.lds_N) + ") only");
         linear_scratch &l = ensure_linear(p, replica, N, eb, ks.front()->dev.device, s);
         void *B = l.buf, *C = (char *)l.buf + linear_c_offset(p->st.K, N, eb);
         gs::launch_tm_in(X, B, p->st.K, N, dtype, s);
@@ -1207,6 +1251,7 @@ int gs_plan_info_get(gs_plan_t *p, gs_plan_info *info) {
             info->ks_head_groups = s.dev.ks ? s.dev.ks_gh : 0;
             info->ks_wpos = s.dev.ks && s.dev.ks_wp ? 1 : 0;
             info->nm_tiles = s.dev.nm ? s.dev.nm_tiles : 0;
+            info->weights = (uint32_t)s.dev.weights;
         }
     });
 }

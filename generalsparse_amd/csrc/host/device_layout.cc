@@ -3,7 +3,9 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
+#include <limits>
 
 namespace gs {
 
@@ -48,6 +50,68 @@ void convert_values(const float *in, uint64_t n, int dtype, void *out) {
     }
     uint16_t *o = static_cast<uint16_t *>(out);
     for (uint64_t i = 0; i < n; i++) o[i] = value_bits16(in[i], dtype);
+}
+
+// ------------------------------------------------------------------ FP8 (OCP e4m3fn) weight values
+// e4m3fn: 1 sign, 4 exponent (bias 7), 3 mantissa bits; subnormals m * 2^-9, largest finite 448 = 0x7e,
+// no infinity, NaN = 0x7f / 0xff.  Integer arithmetic on the fp32 bits: no rounding mode is consulted
+uint8_t f32_to_e4m3_bits(float x) {
+    uint32_t b;
+    std::memcpy(&b, &x, 4);
+    const uint8_t sign = (uint8_t)((b >> 24) & 0x80u);
+    const uint32_t exp = (b >> 23) & 0xffu, man = b & 0x7fffffu;
+    if (exp >= 127u + 9u) return (uint8_t)(sign | 0x7eu);  // |x| >= 512 (a non-finite x too): saturated
+    uint32_t code;
+    if (exp >= 127u - 6u) {  // |x| >= 2^-6: a normal code, the carry of the rounding runs into the exponent
+        code = ((exp - 120u) << 3) | (man >> 20);
+        const uint32_t rem = man & 0xfffffu;
+        if (rem > 0x80000u || (rem == 0x80000u && (code & 1u))) code++;
+    } else {  // below the smallest normal: a multiple of 2^-9 (8 * 2^-9 = 2^-6 is code 8)
+        const uint32_t shift = 141u - exp;  // |x| * 2^9 = sig * 2^-shift, sig < 2^24
+        if (exp == 0u || shift >= 25u) return sign;
+        const uint32_t sig = man | 0x800000u;
+        code = sig >> shift;
+        const uint32_t rem = sig & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        if (rem > half || (rem == half && (code & 1u))) code++;
+    }
+    return (uint8_t)(sign | std::min<uint32_t>(code, 0x7eu));
+}
+
+float e4m3_bits_to_f32(uint8_t c) {
+    const uint32_t e = (c >> 3) & 0xfu, m = c & 7u;
+    float v;
+    if (e == 15u && m == 7u) v = std::numeric_limits<float>::quiet_NaN();
+    else if (e == 0u) v = std::ldexp((float)m, -9);
+    else v = std::ldexp((float)(8u + m), (int)e - 10);
+    return (c & 0x80u) ? -v : v;
+}
+
+float fp8_default_scale(float amax) {
+    if (!(amax > 0.f)) return 1.f;
+    int x = 0;
+    const float f = std::frexp(amax, &x);  // amax = f * 2^x, f in [0.5, 1); 448 = 0.875 * 2^9
+    return std::ldexp(1.f, std::max(f <= 0.875f ? x - 9 : x - 8, -126));
+}
+
+void quantize_fp8_rows(const float *val, const uint64_t *row, uint64_t n, uint64_t n_rows, const float *row_scale,
+                       uint8_t *codes, float *scale) {
+    for (uint64_t i = 0; i < n; i++) {
+        GS_CHECK(row[i] < n_rows, "FP8 weights: a value's row index is past the row count");
+        GS_CHECK(std::isfinite(val[i]), "FP8 weights: a non-finite value of A (e4m3fn has no infinity): value " +
+                                            std::to_string(i) + " of row " + std::to_string(row[i]));
+    }
+    if (row_scale) {
+        for (uint64_t r = 0; r < n_rows; r++) {
+            GS_CHECK(std::isfinite(row_scale[r]) && row_scale[r] > 0.f,
+                     "FP8 weights: row_scale[" + std::to_string(r) + "] must be finite and > 0");
+            scale[r] = row_scale[r];
+        }
+    } else {
+        std::vector<float> amax(n_rows, 0.f);
+        for (uint64_t i = 0; i < n; i++) amax[row[i]] = std::max(amax[row[i]], std::fabs(val[i]));
+        for (uint64_t r = 0; r < n_rows; r++) scale[r] = fp8_default_scale(amax[r]);
+    }
+    for (uint64_t i = 0; i < n; i++) codes[i] = f32_to_e4m3_bits(val[i] / scale[row[i]]);  // an fp32 quotient
 }
 
 // Rows as the matrix-core layouts need them: each row's columns ascending and
@@ -381,10 +445,12 @@ bool build_mfma_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<ui
 
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,
-                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype) {
+                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype,
+                    const std::vector<uint8_t> *codes) {
     const uint64_t nb = tb_rows.size() - 1;
     if (nb == 0 || K == 0) { why = "empty plan"; return false; }
     if (N == 0 || N % 8 != 0) { why = "N must be a multiple of 8"; return false; }
+    GS_CHECK(!codes || codes->size() == vals.size(), "k_mfma_ks layout: one e4m3 code per value");
     // KS_WAVES = 16: twice the waves (more loads in flight per CU) when their stages fit LDS
     uint32_t W = kKsWaves;
     uint64_t rmax = 0;
@@ -558,7 +624,8 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
                         pos.push_back((uint16_t)(i * RS + (col[e] - base)));
                         prow.push_back((uint16_t)i);
                         pcol.push_back((uint16_t)(col[e] - base));
-                        hv.push_back(value_bits16(vals[e], dtype));
+                        // (FP8 weights: the entry's code rides through the ordering in the 16-bit slot)
+                        hv.push_back(codes ? (uint16_t)(*codes)[e] : value_bits16(vals[e], dtype));
                     }
                     cur[i] = e;
                 }
@@ -606,6 +673,10 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
     else
         t.pos.insert(t.pos.end(), 8, (uint16_t)pad_h);  // spare group: loads past a wave's last step
     t.val.insert(t.val.end(), 8, 0);
+    if (codes) {  // 8 bytes per group in place of the 8 x u16 (pad slots: 0, which is code 0)
+        t.val8.assign(t.val.begin(), t.val.end());
+        std::vector<uint16_t>().swap(t.val);
+    }
     return true;
 }
 
@@ -827,7 +898,24 @@ uint32_t nm_tiles_for(uint64_t row_num, int64_t cfg_tiles, uint32_t N) {
     return best;
 }
 
-mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t K, int dtype) {
+void check_fp8_layout(const mc_layout &mc, uint64_t K) {
+    static const char *const names[] = {"a gather family", "k_mfma_rows", "k_mfma_ks", "k_nm_mfma", "k_mfma_bm"};
+    GS_CHECK(mc.kind == mc_layout::KS, std::string("FP8 weights run on k_mfma_ks plans only: this plan compiles to ") +
+                                           names[mc.kind] + (mc.why.empty() ? "" : " (" + mc.why + ")"));
+    const ks_tiles &t = mc.ks;
+    GS_CHECK(t.CT == 2, "FP8 weights: the plan must be built for 17 .. 32 dense columns (32-column tiles), not N = " +
+                            std::to_string(mc.N));
+    GS_CHECK(t.W == kKsWaves && t.AP, "FP8 weights: k_mfma_ks with 8 waves and the apart LDS layout only (KS_WAVES, KS_APART)");
+    GS_CHECK(!t.P8 && !t.WP, "FP8 weights: 16-bit entry positions only (not KS_POS8 / KS_WPOS)");
+    GS_CHECK(get_config().KS_PERSIST <= 0, "FP8 weights: the static grid only (not KS_PERSIST)");
+    GS_CHECK(t.NT <= 1 && ks_tm_fits(t.RT, t.MAXG), "FP8 weights: no k_mfma_ks instantiation for this plan (ks_tm_fits)");
+    GS_CHECK(K % 8 == 0 && K >= 8, "FP8 weights: K must be a multiple of 8, not " + std::to_string(K));
+    GS_CHECK(t.val.empty() && t.val8.size() == t.pos.size() && !mc.w8_scale.empty(),
+             "FP8 weights: the layout holds no 8-bit values");
+}
+
+mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t K, int dtype,
+                                    const fp8_request *w8) {
     mc_layout L;
     const config_t cfg = get_config();
     const int64_t Nd = cfg.DENSE_MATRIX_SIZE;
@@ -884,8 +972,18 @@ mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &s
         L.kind = mc_layout::BM;
         return L;
     }
+    // FP8 weights: the canonical values (repeated coordinates summed) quantised row by row
+    std::vector<uint8_t> codes;
+    if (w8) {
+        std::vector<uint64_t> vrow(cr.val.size());
+        for (uint64_t r = 0; r < row_num; r++)
+            for (uint32_t e = cr.rp[r]; e < cr.rp[r + 1]; e++) vrow[e] = r;
+        codes.resize(cr.val.size());
+        L.w8_scale.resize(row_num);
+        quantize_fp8_rows(cr.val.data(), vrow.data(), cr.val.size(), row_num, w8->row_scale, codes.data(), L.w8_scale.data());
+    }
     if (cfg.MFMA_KS && build_ks_tiles(L.tbr, cr.rp, cr.col, cr.val, K, N, cfg.KS_SPLIT, cfg.KS_MIN_ROWS, cfg.MFMA_MAX_FILL,
-                                      L.ks, L.why, dtype)) {
+                                      L.ks, L.why, dtype, w8 ? &codes : nullptr)) {
         L.kind = mc_layout::KS;
         return L;
     }

@@ -34,6 +34,30 @@ inline uint16_t value_bits16(float f, int dtype) { return dtype == kBF16 ? f32_t
 // gs_convert_values: n values into the dtype's storage type (float or 16-bit words)
 void convert_values(const float *in, uint64_t n, int dtype, void *out);
 
+// ---- FP8 weight values (GS_W_FP8_E4M3): A's values of a k_mfma_ks plan as OCP e4m3fn codes, one
+// byte each, and one fp32 scale per row of A: value = decode(code) * scale[row].  B, C, bias, residual and
+// the accumulation stay the plan dtype's (fp16 in, fp32 sums, one rounding).
+constexpr int kWNative = 0, kWFp8 = 1;  // include/generalsparse.h GS_W_NATIVE / GS_W_FP8_E4M3
+// fp32 -> e4m3fn code, round to nearest even, saturated at +-448 (0x7e / 0xfe); x finite.  The NaN
+// codes 0x7f / 0xff are never produced
+uint8_t f32_to_e4m3_bits(float x);
+// e4m3fn code -> fp32 (exact; 0x7f / 0xff: NaN)
+float e4m3_bits_to_f32(uint8_t c);
+// the default scale of a row whose largest magnitude is amax: 2^e with the smallest integer e such
+// that amax / 2^e <= 448 (amax / scale in (224, 448]), from amax's exponent and fraction (frexp), never
+// through a logarithm; amax == 0: 1.  e is kept at -126 or above, so the scale is a normal fp32
+float fp8_default_scale(float amax);
+// gs_quantize_fp8_rows: codes[i] = e4m3(val[i] / scale[row[i]]) (an IEEE fp32 division).  row_scale null:
+// scale[r] = fp8_default_scale(max |val| of row r), 1 for a row without values; else the caller's n_rows
+// scales, each finite and > 0.  Refused: a non-finite value (e4m3fn has no infinity), a row index past
+// n_rows, a bad scale.  scale: n_rows entries
+void quantize_fp8_rows(const float *val, const uint64_t *row, uint64_t n, uint64_t n_rows, const float *row_scale,
+                       uint8_t *codes, float *scale);
+// FP8 weights asked of choose_matrix_core_layout: the caller's scales (null: the default rule)
+struct fp8_request {
+    const float *row_scale = nullptr;
+};
+
 struct canon_rows {
     std::vector<uint32_t> rp;
     std::vector<uint64_t> col;
@@ -81,6 +105,7 @@ struct ks_tiles {
     uint32_t GH = 0;  // groups per head step (0: no head region)
     size_t lds_bytes = 0;
     std::vector<uint16_t> pos, val;  // 8 u16 per group each
+    std::vector<uint8_t> val8;       // FP8 weights: 8 e4m3 codes per group in place of val (pad slots: code 0)
     std::vector<uint8_t> pos8;       // P8 / WP: 8 bytes per group
     std::vector<uint8_t> win;        // WP: one window byte per group
     std::vector<uint32_t> steps;     // per (unit, k-step): first group, group count
@@ -123,7 +148,8 @@ inline std::vector<uint32_t> ks_tm_tile_split(uint32_t n_tokens, uint32_t cap) {
 
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,
-                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype = kF16);
+                    int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype = kF16,
+                    const std::vector<uint8_t> *codes = nullptr);  // codes: vals' e4m3 codes -> t.val8, t.val left empty
 
 // k_mfma_bm upload layout: unit u = (BMTB g, K range q) of NS 32-column k-steps; per
 // (u*NS + step)*64 + lane one 8-byte record (rec[2i] = mask bytes of tiles 0..3, rec[2i+1]
@@ -177,8 +203,16 @@ struct mc_layout {
     bool nm4 = false;                      // k_nm_mfma4 (256-row workgroups of 8 waves, K split, B by LDS-DMA)
     bool nm_nt = false;                    // k_nm_mfma: A's panel blocks by non-temporal loads (NM_NT)
     uint32_t nm_split = 1, nm_ncs = 0;     // ... K ranges per row block, 256-column chunks per range
+    std::vector<float> w8_scale;  // FP8 weights (KS): the scale of every row of the plan
     std::string why;  // why NONE
 };
-mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t K, int dtype);
+// w8 (null: the dtype's own values): a k_mfma_ks layout gets ks.val8 and w8_scale instead of ks.val; the
+// caller checks the layout with check_fp8_layout
+mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t K, int dtype,
+                                    const fp8_request *w8 = nullptr);
+// FP8 weights run on k_mfma_ks in the release layout only (CT = 2: a plan built for 17 .. 32 columns, 8
+// waves, the apart layout, 16-bit positions, the static grid, ks_tm_fits, K % 8 == 0): throws a gs_error
+// that names the condition a layout misses
+void check_fp8_layout(const mc_layout &mc, uint64_t K);
 
 }  // namespace gs

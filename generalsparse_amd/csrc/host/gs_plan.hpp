@@ -19,6 +19,7 @@ struct device_arrays {
     void *pad_out = nullptr;  // row-padded plans: scratch output of all the plan's rows
     void *tcol = nullptr, *tval = nullptr;  // LDS tile layout (k_lds_rows)
     void *tw = nullptr;  // k_mfma_ks with window positions (KS_WPOS): one window byte per group
+    float *wscale = nullptr;  // k_mfma_ks with FP8 weights: one fp32 scale per row of A (per replica, as tval is)
     uint32_t *t0 = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *t4 = nullptr;
     uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;
     uint64_t *m0 = nullptr;
@@ -37,6 +38,7 @@ enum { MP_PART_COL, MP_PART_VAL, MP_PART_WZ, MP_PART_WQ, MP_PART_ENDS, MP_PART_R
 struct device_plan {
     int device = 0;
     int dtype = 1;         // 0 fp32, 1 fp16, 2 bf16 (values, B and C; device_layout.hpp kF32 / kF16 / kBF16)
+    int weights = 0;       // 0 A's values in the dtype, 1 e4m3 codes + a scale per row (kWNative / kWFp8; k_mfma_ks, fp16)
     int col_bytes = 2;     // 2 (u16) or 4 (u32)
     int scf = 4;           // sparse entries per vector load
     bool needs_memset = false;
@@ -137,7 +139,10 @@ std::shared_ptr<meta_data_set> load_plan(const std::string &path, std::vector<lo
                                          std::string &pipeline);
 
 // device_plan.hip
-void upload_plan(plan_state &p, int dtype, int device);
+// weights (kWNative / kWFp8), row_scale (kWFp8: null or M scales): gs_plan_upload_ex's.  An FP8 upload is
+// refused, before anything is allocated, unless the plan is the undivided matrix without padded rows,
+// the dtype fp16 and the layout one check_fp8_layout admits
+void upload_plan(plan_state &p, int dtype, int device, int weights = kWNative, const float *row_scale = nullptr);
 void add_replica(plan_state &p);
 void free_device(plan_state &p);
 // zero rows [lo, hi) of a row-major C of width N, element size e (sub-matrix executor)
@@ -171,6 +176,12 @@ void launch_gather(const plan_state &p, const device_arrays &a, const void *B, v
 // ks_launch.hip: k_mfma_ks (K-split, wave-autonomous matrix-core row blocks)
 void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
                const gsk::epilogue &epi = gsk::epilogue_identity());
+// ks_w8_launch.hip / ks_tm_w8_launch.hip: the FP8-weight forms (k_mfma_ks_w8, k_mfma_ks_tm with VB = 8) behind
+// launch_ks and launch_linear_fused, for plans uploaded with kWFp8 (same arguments, plus the replica's scales)
+void launch_ks_w8(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
+                  const gsk::epilogue &epi);
+void launch_ks_tm_w8(const plan_state &p, const device_arrays &a, const void *X, void *Y, uint32_t N, hipStream_t s,
+                     const gsk::epilogue &epi, float *slabs, uint32_t *arrivals);
 // ks_tm_launch.hip: k_mfma_ks_tm, a k_mfma_ks plan on token-major activations (gs_linear: Y = X * A^T,
 // X: n_tokens x K, Y: n_tokens x M).  linear_fuses: the plan and its upload layout are ones the kernel
 // is built for (a plan of 17 .. 32 tokens -- 32-token tiles -- 8 waves, 16-bit positions, K % 8 == 0,

@@ -283,9 +283,12 @@ void upload_ks(upload_ctx &u) {
     GS_CHECK(!(kt.WP && d.ks_persist), "KS_WPOS: window positions are not built for the persistent grid (KS_PERSIST)");
     a.tcol = kt.P8 || kt.WP ? (void *)dev_copy(d, kt.pos8) : (void *)dev_copy(d, kt.pos);
     if (kt.WP) a.tw = dev_copy(d, kt.win);
-    a.tval = dev_copy(d, kt.val);
+    // FP8 weights: 8 bytes per group (e4m3 codes) in place of the 8 x u16
+    a.tval = d.weights == kWFp8 ? (void *)dev_copy(d, kt.val8) : (void *)dev_copy(d, kt.val);
     a.t1 = dev_copy(d, kt.steps);
     d.bytes_tile = d.bytes_A - before;
+    // ... and the rows' scales (M fp32, indexed as the epilogue's bias is): bytes of A, not of its tiles
+    if (d.weights == kWFp8) a.wscale = dev_copy(d, mc.w8_scale);
     if (kt.S > 1) {  // the error word: ks_slab_wait
         const uint32_t CT = kt.CT, nt = ks_col_tiles_ct(mc.N, CT);
         upload_ksplit_state(d, a, (size_t)nb * kt.S * nt * 256 * kt.RT * CT, (size_t)nb * nt, true);
@@ -634,9 +637,12 @@ void upload_merge_path(upload_ctx &u) {
 
 }  // namespace
 
-void upload_plan(plan_state &p, int dtype, int device) {
+void upload_plan(plan_state &p, int dtype, int device, int weights, const float *row_scale) {
     GS_CHECK(p.cg && p.cg->is_compiled(), "plan must be compiled before upload");
     GS_CHECK(dtype_ok(dtype), "dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)");
+    GS_CHECK(weights == kWNative || weights == kWFp8, "weights must be 0 (native) or 1 (FP8 e4m3)");
+    GS_CHECK(weights == kWFp8 || !row_scale, "row_scale goes with FP8 weights");
+    GS_CHECK(weights != kWFp8 || dtype == kF16, "FP8 weights run with fp16 activations only (dtype f16), not bf16 / f32");
     free_device(p);
     HIP_OK(hipSetDevice(device));
     const kernel_spec &sp = p.cg->get_kernel_spec();
@@ -666,8 +672,16 @@ void upload_plan(plan_state &p, int dtype, int device) {
     GS_CHECK(nnz < 0xffffffffull - kPad, "nnz exceeds 32-bit offsets");
     d.nnz_stored = nnz;
     device_arrays a;
+    // FP8 weights: every refusal before the first allocation (the plan is then simply not uploaded)
+    const fp8_request w8{row_scale};
+    if (weights == kWFp8) {
+        GS_CHECK(sb == 0 && !pidx, "FP8 weights: an undivided plan only (this is a sub-matrix of a row division)");
+        GS_CHECK(row_num_of_sub_matrix(m, sb) == p.M, "FP8 weights: a plan without padded rows only");
+    }
     // the matrix-core layout (device_layout.cc: the same choice the emitted program makes)
-    const mc_layout mc = choose_matrix_core_layout(m, sp, sb, p.K, dtype);
+    const mc_layout mc = choose_matrix_core_layout(m, sp, sb, p.K, dtype, weights == kWFp8 ? &w8 : nullptr);
+    if (weights == kWFp8) check_fp8_layout(mc, p.K);
+    d.weights = weights;
     if (mc.kind == mc_layout::NM) {
         upload_nm(d, a, mc, m.u(THREAD_META, "first_nz_indices", sb).size() - 1);
         d.replicas.push_back(a);
@@ -766,6 +780,7 @@ void add_replica(plan_state &p) {
     r.tcol = dup(s.tcol);
     r.tval = dup(s.tval);
     r.tw = dup(s.tw);
+    r.wscale = (float *)dup(s.wscale);
     r.t0 = (uint32_t *)dup(s.t0);
     r.t1 = (uint32_t *)dup(s.t1);
     r.t2 = (uint32_t *)dup(s.t2);
@@ -895,6 +910,9 @@ void launch_spmm(plan_state &p, int replica, const void *B, void *C, uint32_t N,
              "launch_spmm: this plan and width take the epilogue as a post-pass (launch_epilogue)");
     GS_CHECK(replica >= 0 && (size_t)replica < p.dev.replicas.size(), "bad replica index");
     GS_CHECK(N >= 1, "N >= 1");
+    // (the CSR fall-back at another width would need a second, differently rounded copy of A)
+    GS_CHECK(p.dev.weights != kWFp8 || N == p.dev.lds_N,
+             "a plan with FP8 weights runs at the width it was built for (N = " + std::to_string(p.dev.lds_N) + ") only");
     if (p.dev.pad_rows) {
         GS_CHECK(N <= p.dev.pad_N, "row-padded plan built for N=" + std::to_string(p.dev.pad_N) +
                                        ": its scratch output holds no wider B (re-run the pipeline for this N)");

@@ -31,6 +31,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
                  uint64_t *stamps = nullptr, const gsk::epilogue &epi = gsk::epilogue_identity()) {
     const device_plan &d = p.dev;
     constexpr bool F16 = std::is_same<ET, gsk::f16>::value;
+    GS_CHECK(d.weights == kWNative, "k_mfma_ks reads 16-bit values: a plan with FP8 weights runs k_mfma_ks_w8 (launch_ks)");
     if constexpr (!F16) {
         static_assert(W == (int)kKsWaves && !STAMPS, "bf16: the release instantiations only");
         GS_CHECK(d.waves == kKsWaves && !d.ks_p8 && d.ks_ap && !d.ks_persist,
@@ -445,6 +446,7 @@ uint32_t ks_group_key(const plan_state &p, uint32_t N) {
     const device_plan &d = p.dev;
     const bool w8 = d.waves == kKsWaves && d.ks_ap, w4 = d.waves == 4 && !d.ks_ap;
     if (!p.uploaded || !d.mfma || !d.ks || d.pad_rows || N != 32 || d.lds_N != 32 || !(w8 || w4) || d.ks_persist) return 0;
+    if (d.weights != kWNative) return 0;  // FP8 weights: no grouped kernel is built, a batch runs single launches
     // bf16: the grouped kernel's twins are the release instantiations (as launch_ks_k)
     if (d.dtype == kBF16 && (d.ks_p8 || d.ks_wp || !w8)) return 0;
     if (d.ks_wp && !w8) return 0;
@@ -475,7 +477,8 @@ void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void 
     GS_CHECK(p.dev.ks_ctw == ks_ct_rt(N, p.dev.maxr) || (p.dev.ks_ctw == 4 && ks_ct_rt(N, p.dev.maxr) == 8 &&
                                                          !ks_ct8_fits(p.dev.maxr, p.dev.seg_cap)),
              "k_mfma_ks: column tiles disagree with the upload");
-    if (p.dev.dtype == kBF16) launch_ks_bf16(p, a, B, C, N, s, epi);
+    if (p.dev.weights == kWFp8) launch_ks_w8(p, a, B, C, N, s, epi);  // ks_w8_launch.hip
+    else if (p.dev.dtype == kBF16) launch_ks_bf16(p, a, B, C, N, s, epi);
     else launch_ks_et<gsk::f16>(p, a, B, C, N, s, epi);
 }
 

@@ -14,6 +14,7 @@ template <int RT, int MAXG, class ET>
 void launch_ks_tm_k(const plan_state &p, const device_arrays &a, const ET *X, ET *Y, uint32_t N, hipStream_t s,
                     const gsk::epilogue &epi, float *slabs, uint32_t *arrivals) {
     const device_plan &d = p.dev;
+    GS_CHECK(d.weights == kWNative, "k_mfma_ks_tm reads 16-bit values: a plan with FP8 weights runs its VB = 8 form (launch_ks_tm_w8)");
     if constexpr (!ks_tm_fits(RT, MAXG)) {
         throw gs_error("k_mfma_ks_tm: instantiation not built for this plan (linear_fuses)");
     } else {
@@ -92,7 +93,8 @@ void launch_linear_fused(const plan_state &p, int replica, const void *X, void *
     GS_CHECK(linear_fuses(p, n_tokens) && (uintptr_t)X % 16 == 0, "k_mfma_ks_tm: not a plan or operand it runs (linear_fuses)");
     GS_CHECK(replica >= 0 && (size_t)replica < p.dev.replicas.size(), "bad replica index");
     const device_arrays &a = p.dev.replicas[(size_t)replica];
-    if (p.dev.dtype == kBF16) launch_ks_tm_bf16(p, a, X, Y, n_tokens, s, epi, slabs, arrivals);
+    if (p.dev.weights == kWFp8) launch_ks_tm_w8(p, a, X, Y, n_tokens, s, epi, slabs, arrivals);  // ks_tm_w8_launch.hip
+    else if (p.dev.dtype == kBF16) launch_ks_tm_bf16(p, a, X, Y, n_tokens, s, epi, slabs, arrivals);
     else launch_ks_tm_et<gsk::f16>(p, a, X, Y, n_tokens, s, epi, slabs, arrivals);
 }
 #endif  // !GS_KS_BF16_OBJECT

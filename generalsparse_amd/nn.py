@@ -7,7 +7,7 @@ Inference only: the engine has no backward pass."""
 import numpy as np
 import torch
 
-from . import Plan, _check_activation, _dtype_code, _torch_dtype
+from . import GS_W_FP8_E4M3, Plan, _check_activation, _dtype_code, _torch_dtype, _weights_code
 
 
 class SparseLinear(torch.nn.Module):
@@ -35,13 +35,16 @@ class SparseLinear(torch.nn.Module):
 
     @classmethod
     def from_dense(cls, weight, bias=None, *, tokens=32, dtype="f16", pipeline=("block_total", 40, 1), activation=None,
-                   device=0, upload=True):
+                   device=0, upload=True, weights=None, row_scale=None):
         """the plan from the non-zeros of a pruned (out, in) weight: from_coo, run_pipeline at
         N = tokens, compile, upload (upload=False stops before the device: the plan can be inspected,
         the module cannot run).  tokens: the tile width (17 .. 32 for the one-kernel path), whatever
-        token counts forward will see"""
+        token counts forward will see.  weights="fp8" (with row_scale: one scale per output feature, or
+        the default power-of-two rule): the weight's values as e4m3 codes, Plan.upload's weight-only
+        quantisation -- activations, bias and output stay `dtype`, which must be f16"""
         _check_activation(activation)
         _dtype_code(dtype)
+        _weights_code(weights)
         w = torch.as_tensor(weight).detach().to("cpu", torch.float32).numpy()
         if w.ndim != 2:
             raise ValueError("weight must be (out_features, in_features)")
@@ -50,7 +53,7 @@ class SparseLinear(torch.nn.Module):
         plan = Plan.from_coo(w.shape[0], w.shape[1], r.astype(np.uint64), c.astype(np.uint64), w[r, c])
         plan.run_pipeline(name, int(tokens), int(p0), int(p1)).compile()
         if upload:
-            plan.upload(dtype, int(device))
+            plan.upload(dtype, int(device), weights=weights, row_scale=row_scale)
             if bias is not None:
                 bias = torch.as_tensor(bias).detach().to(torch.device("cuda", int(device)), torch.float32)
         layer = cls(plan, bias, activation)
@@ -87,4 +90,6 @@ class SparseLinear(torch.nn.Module):
             s += f", linear_fused({self.tokens})={self.plan.linear_fused(self.tokens)}"
         if info["replicas"]:
             s += f", dtype={_torch_dtype(info['dtype'])}"
+            if info["weights"] == GS_W_FP8_E4M3:
+                s += ", weights=fp8_e4m3"
         return s

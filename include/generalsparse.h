@@ -74,6 +74,7 @@ typedef struct {
     uint32_t ks_head_groups;      /* k_mfma_ks: groups per head step (KS_HEAD; 0: every step by record) */
     uint32_t nm_tiles;            /* k_nm_mfma: 16-row tiles per workgroup (NM_TILES / the upload's rule) */
     uint32_t ks_wpos;             /* k_mfma_ks: one-byte window positions (KS_WPOS; 0: the u16 layout) */
+    uint32_t weights;             /* GS_W_NATIVE / GS_W_FP8_E4M3, as uploaded (tile_bytes / device_bytes_A: the true bytes) */
 } gs_plan_info;
 
 const char *gs_last_error(void);
@@ -121,6 +122,37 @@ int gs_plan_upload(gs_plan_t *p, int dtype, int device);
  * NaN stays a quiet NaN, +-Inf stay, values past the largest finite value round to +-Inf.
  * Host only (no device is touched). */
 int gs_convert_values(const float *in, uint64_t n, int dtype, void *out);
+/* How A's values are held on the device.  GS_W_NATIVE: in the plan's dtype (gs_plan_upload).
+ * GS_W_FP8_E4M3: one OCP e4m3fn code per stored value and one fp32 scale per row of A, value =
+ * decode(code) * scale[row] -- 3 instead of 4 bytes per stored entry of a k_mfma_ks plan.  B, C, bias,
+ * residual and the accumulation stay GS_F16's: the kernel decodes the codes to fp16 (exact: every finite
+ * e4m3 value is an fp16 value), runs the MFMAs of the fp16 plan in their order and multiplies the fp32
+ * sum of a row by its scale before the epilogue and the one rounding.  With power-of-two scales (the
+ * default rule) the result is bit for bit that of a GS_W_NATIVE fp16 plan of the dequantised values.
+ * row_scale: NULL (scale[r] = 2^e, the smallest e with max|A[r, :]| / 2^e <= 448; 1 for a row without
+ * values) or one finite scale > 0 per row of A.
+ * Accepted only for an undivided plan without padded rows that compiles to k_mfma_ks in its release layout
+ * (built for 17 .. 32 dense columns, 8 waves, 16-bit positions, the static grid), dtype GS_F16, K a multiple
+ * of 8; every other plan, a non-finite value of A or a bad scale is refused (GS_ERR, the condition in
+ * gs_last_error) before anything is allocated: the plan is then not on the device.  Such a plan runs
+ * gs_spmm / gs_spmm_ex at the width it was built for only, gs_linear at any token count (the three-launch
+ * path at that width only), and a batch runs it as single launches. */
+enum { GS_W_NATIVE = 0, GS_W_FP8_E4M3 = 1 };
+int gs_plan_upload_ex(gs_plan_t *p, int dtype, int weights, const float *row_scale, int device);
+/* The quantiser of GS_W_FP8_E4M3, host only: codes[i] = e4m3(val[i] / scale[row[i]]), an IEEE fp32
+ * division rounded to nearest even and saturated at +-448 (codes 0x7f / 0xff, NaN, are never written).
+ * row[i] < n_rows is the row of val[i]; row_scale NULL: the default rule above, else n_scale == n_rows
+ * scales.  scale (n_rows entries) receives the scales used.  Refused: a non-finite value, a row index
+ * past n_rows, a scale that is not finite and > 0, n_scale != n_rows. */
+int gs_quantize_fp8_rows(const float *val, const uint64_t *row, uint64_t n, uint64_t n_rows, const float *row_scale,
+                         uint64_t n_scale, uint8_t *codes, float *scale);
+/* e4m3fn codes to fp32 (exact; 0x7f / 0xff give NaN).  Host only. */
+int gs_fp8_decode(const uint8_t *codes, uint64_t n, float *out);
+/* The 8-bit value array (8 codes per entry group, in the order of the plan's k_mfma_ks groups) and the
+ * n_rows scales exactly as gs_plan_upload_ex(GS_F16, GS_W_FP8_E4M3, row_scale) would lay them out for
+ * this compiled plan under the current config, without touching a device; its refusals are the upload's.
+ * *n_codes receives the array's length; codes / scale are written when cap holds it. */
+int gs_plan_fp8_layout(gs_plan_t *p, const float *row_scale, uint8_t *codes, uint64_t cap, uint64_t *n_codes, float *scale);
 int gs_plan_add_replica(gs_plan_t *p);
 /* C = A * B.  B: K x N row-major, C: M x N row-major, device pointers of the
  * plan's dtype (float, fp16 or bf16 elements: GS_F32 / GS_F16 / GS_BF16; every kernel
