@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import GS_BF16, GS_F16, GS_F32, GS_W_FP8_E4M3, GS_W_NATIVE, GsError
 
 __all__ = ["Plan", "Batch", "Rotation", "SparseLinear", "set_config", "GsError", "GS_F16", "GS_F32", "GS_BF16", "PIPELINES", "load_library",
-           "convert_values", "GS_W_NATIVE", "GS_W_FP8_E4M3", "fp8_quantize", "fp8_decode"]
+           "convert_values", "GS_W_NATIVE", "GS_W_FP8_E4M3", "fp8_quantize", "fp8_decode", "sddmm_geometry"]
 
 # token_test.cc pipelines (+ the two compositions this engine adds)
 PIPELINES = ("thread_total", "warp_total", "block_total", "thread_bit_map", "warp_segment",
@@ -121,6 +121,15 @@ def fp8_decode(codes):
     out = np.zeros(c.size, np.float32)
     _lib.check(L.gs_fp8_decode(c.ravel().ctypes.data_as(_lib.u8p), c.size, out.ctypes.data_as(_lib.f32p)))
     return out.reshape(c.shape)
+
+
+def sddmm_geometry():
+    """(row_block, col_strip, token_chunk) of k_sddmm_tm (gs_sddmm_geometry): output features per
+    workgroup, input features per wave strip, tokens per chunk"""
+    L = _lib.load()
+    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(L.gs_sddmm_geometry(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return a.value, b.value, c.value
 
 
 def _torch_dtype(code):
@@ -423,6 +432,7 @@ class Plan:
         spmm at the width it was built for and linear at any token count; with power-of-two scales the
         results are bit for bit those of an f16 plan of fp8_decode(codes) * scale[row]."""
         self.dtype_code = _dtype_code(dtype)
+        self._device = int(device)
         w = _weights_code(weights)
         if w == GS_W_NATIVE:
             if row_scale is not None:
@@ -526,6 +536,72 @@ class Plan:
         s = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
         _lib.check(self._L.gs_linear(self._h, int(replica), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), n,
                                      ctypes.byref(epi) if epi is not None else None, ctypes.c_void_p(s)))
+        return out
+
+    # ------------------------------------------------------------- backward
+    def _pattern(self):
+        n = ctypes.c_uint64(0)
+        _lib.check(self._L.gs_plan_pattern(self._h, None, None, None, 0, ctypes.byref(n)))
+        row, col, val = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64), np.zeros(n.value, np.float32)
+        if n.value:
+            _lib.check(self._L.gs_plan_pattern(self._h, row.ctypes.data_as(_lib.u64p), col.ctypes.data_as(_lib.u64p),
+                                               val.ctypes.data_as(_lib.f32p), n.value, ctypes.byref(n)))
+        return row, col, val
+
+    def pattern(self):
+        """(row, col) of the plan's entries as uint64 arrays in the canonical order: by original row, then
+        by column, stored duplicates adjacent in input order -- np.nonzero's order for a dense weight.
+        The same after any pipeline; no device is touched (gs_plan_pattern)"""
+        row, col, _ = self._pattern()
+        return row, col
+
+    def values(self):
+        """the float32 values the plan holds, in pattern()'s order"""
+        return self._pattern()[2]
+
+    def sddmm_prepare(self):
+        """uploads the pattern for sddmm now (gs_plan_sddmm_prepare): once per plan; needed before a
+        stream capture that holds the plan's first sddmm"""
+        _lib.check(self._L.gs_plan_sddmm_prepare(self._h))
+        return self
+
+    def sddmm(self, g, x, out=None, stream=None):
+        """out[e] = sum_t g[t, row_e] * x[t, col_e] over pattern()'s entries (gs_sddmm, k_sddmm_tm): the
+        gradient of linear with respect to the weight's stored values.  g: (n, M) and x: (n, K), contiguous
+        GPU tensors of the plan's dtype (f16 or bf16; an f32 plan is refused) on the plan's device, n >= 1;
+        out: a contiguous float32 tensor of nnz elements there (allocated when None).  fp32 sums in one
+        fixed order: the same bits on every call.  Every argument is checked before the call, so a
+        refused call leaves out untouched."""
+        import torch
+        info = self.info()
+        M, K, nnz = info["rows"], info["cols"], info["nnz"]
+        for name, t, feat in (("g", g, M), ("x", x, K)):
+            if not (isinstance(t, torch.Tensor) and t.dim() == 2 and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous 2-D tensor")
+            if t.shape[1] != feat:
+                raise ValueError(f"{name} has {t.shape[1]} columns, expected {feat}")
+            if t.dtype not in (torch.float16, torch.bfloat16):
+                raise TypeError(f"{name} must be float16 or bfloat16 (the plan's dtype)")
+        n = int(g.shape[0])
+        if x.shape[0] != n or n < 1:
+            raise ValueError("g and x must hold the same number of tokens, at least one")
+        if not info["replicas"]:
+            raise _refused("sddmm: plan is not on the device")
+        want = _torch_dtype(info["dtype"])
+        if g.dtype != want or x.dtype != want:
+            raise TypeError(f"g and x must be {want}")
+        dev = getattr(self, "_device", None)
+        for name, t in (("g", g), ("x", x)):
+            if not t.is_cuda or t.device != g.device or (dev is not None and t.device.index != dev):
+                raise ValueError(f"{name} must be a GPU tensor on the plan's device")
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == g.device
+                                    and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == nnz):
+            raise ValueError(f"out must be a contiguous float32 tensor of {nnz} elements on {g.device}")
+        if out is None:
+            out = torch.empty(nnz, dtype=torch.float32, device=g.device)
+        s = stream if stream is not None else torch.cuda.current_stream(g.device).cuda_stream
+        _lib.check(self._L.gs_sddmm(self._h, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(x.data_ptr()), n,
+                                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(s)))
         return out
 
     def linear_fused(self, n):

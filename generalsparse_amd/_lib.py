@@ -61,6 +61,10 @@ SIGNATURES = {
     "gs_plan_linear_launches": ([ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
     "gs_linear_tile_split": ([ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
                               ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
+    "gs_plan_pattern": ([ctypes.c_void_p, u64p, u64p, f32p, ctypes.c_uint64, u64p], ctypes.c_int),
+    "gs_sddmm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "gs_plan_sddmm_prepare": ([ctypes.c_void_p], ctypes.c_int),
+    "gs_sddmm_geometry": ([ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "gs_plan_logical_check": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int], ctypes.c_int),
     "gs_plan_array_set_u64": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
     "gs_last_error": ([], ctypes.c_char_p),

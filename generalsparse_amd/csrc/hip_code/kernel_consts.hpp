@@ -147,4 +147,13 @@ GSK_HD constexpr size_t nm4_lds_bytes(uint32_t CT) {
 // k_merge_path: nonzeros per slot per round
 constexpr uint32_t kMpItems = 8;
 
+// k_sddmm_tm (sddmm.hpp; gs_sddmm): a workgroup of kSddmmWaves waves owns 16 * kSddmmRT output features,
+// each wave a strip of 16 * kSddmmCT input features, tokens in chunks of kSddmmChunk (gs_sddmm_geometry)
+constexpr int kSddmmRT = 4, kSddmmCT = 4, kSddmmWaves = 4;
+constexpr uint32_t kSddmmChunk = 32;
+// a [token][feature] LDS image of one chunk, 16 * T features wide: rows of 32 * T data bytes at a stride
+// of 32 more, each group of 8 rows 128 B further on (the transposed fragment reads are conflict-free)
+GSK_HD constexpr uint32_t sddmm_row_off(uint32_t T, uint32_t t) { return (32u * T + 32u) * t + 128u * (t >> 3); }
+GSK_HD constexpr uint32_t sddmm_image_bytes(uint32_t T) { return (sddmm_row_off(T, kSddmmChunk - 1) + 32u * T + 63u) / 64u * 64u; }
+
 }  // namespace gsk

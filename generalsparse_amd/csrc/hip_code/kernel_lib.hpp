@@ -34,6 +34,8 @@
 //   k_mfma_ks[_group] the same with K split over workgroups
 //   mfma_ks_tm.hpp:
 //   k_mfma_ks_tm     a k_mfma_ks plan on token-major activations (gs_linear: Y = X * A^T)
+//   sddmm.hpp:
+//   k_sddmm_tm       the sampled product G^T * X at a plan's pattern, token-major operands (gs_sddmm)
 //   nm_mfma.hpp:
 //   k_nm_mfma        2:4 panels on the sparse matrix cores
 //   merge_path.hpp:
@@ -51,6 +53,7 @@
 #include "mfma_rows.hpp"
 #include "mfma_ks.hpp"
 #include "mfma_ks_tm.hpp"
+#include "sddmm.hpp"
 #include "nm_mfma.hpp"
 #include "merge_path.hpp"
 #ifdef GS_EXPERIMENTS  // opt-in kernels measured slower than the default ones

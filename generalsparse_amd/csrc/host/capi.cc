@@ -2,6 +2,7 @@
 #include "../../../include/generalsparse.h"
 #include "gs_plan.hpp"
 #include "index_compress.hpp"
+#include "sddmm_layout.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -51,7 +52,16 @@ struct linear_ks_state {
     bool captured = false;    // a captured launch may replay between any two calls: `last` is never known again
 };
 
+// the device form of the plan's pattern (gs_sddmm): one per plan, whatever its replicas
+struct sddmm_state {
+    uint32_t *rp = nullptr;  // M + 1 offsets
+    void *cols = nullptr;    // nnz columns, u16 or u32 (col_bytes)
+    int col_bytes = 0, device = 0;
+};
+
 struct gs_plan {
+    gs::sddmm_pattern pat;  // the pattern in canonical order, taken before any operator ran (snapshot_pattern)
+    sddmm_state sd;
     std::vector<linear_scratch> lin;  // per replica; allocated on first use, freed with the plan
     std::vector<linear_ks_state> lin_ks;  // per replica, likewise
     int lin_device = 0;
@@ -85,6 +95,30 @@ void init_plan(gs::plan_state &s, std::shared_ptr<gs::meta_data_set> m) {
     s.M = s.meta->scalar(gs::GLOBAL_META, "origin_row_num", -1);
     s.K = s.meta->scalar(gs::GLOBAL_META, "origin_col_num", -1);
     s.nnz = s.meta->scalar(gs::GLOBAL_META, "origin_nnz_num", -1);
+}
+
+// The plan's pattern (gs_plan_pattern, gs_sddmm) from sub-matrix 0's COO.  Taken when the plan is created,
+// before any operator runs, so no pipeline's padding entries, row order or storage order reaches it.  A
+// plan read from a plan file holds the COO as its pipeline left it: rows are mapped back through
+// original_nz_row_indices, and a file whose pipeline added padding entries (more stored entries than
+// the matrix has) or divided the matrix leaves the plan without a pattern
+void snapshot_pattern(gs_plan *p) {
+    const gs::meta_data_set &m = *p->st.meta;
+    p->pat = gs::sddmm_pattern();
+    if (!m.is_exist(gs::GLOBAL_META, "nz_col_indices", 0) || !m.is_exist(gs::GLOBAL_META, "nz_vals", 0)) return;
+    const auto &row = m.u(gs::GLOBAL_META, "nz_row_indices", 0), &col = m.u(gs::GLOBAL_META, "nz_col_indices", 0);
+    const auto &val = m.get_element(gs::GLOBAL_META, "nz_vals", 0)->meta_data_arr->f();
+    if (row.size() != p->st.nnz || col.size() != row.size() || val.size() != row.size()) return;
+    const std::vector<uint64_t> *order =
+        m.is_exist(gs::GLOBAL_META, "original_nz_row_indices", 0) ? &m.u(gs::GLOBAL_META, "original_nz_row_indices", 0) : nullptr;
+    try {
+        p->pat = gs::build_sddmm_pattern(p->st.M, row.size(), row.data(), col.data(), val.data(), order ? order->data() : nullptr,
+                                         order ? order->size() : 0);
+    } catch (const gs::gs_error &) {
+        // (a matrix past the pattern's 32-bit offsets, a file with rows it cannot map: the plan itself stands,
+        // gs_plan_pattern and gs_sddmm then refuse it)
+        p->pat = gs::sddmm_pattern();
+    }
 }
 
 uint64_t global_scalar(const gs::plan_state &s, const char *n, int sub) { return s.meta->scalar(gs::GLOBAL_META, n, sub); }
@@ -239,6 +273,13 @@ void free_linear(gs_plan *p) {
     p->lin_ks.clear();
 }
 
+void free_sddmm(gs_plan *p) {
+    if (p->sd.rp || p->sd.cols) (void)hipSetDevice(p->sd.device);
+    if (p->sd.rp) (void)hipFree(p->sd.rp);
+    if (p->sd.cols) (void)hipFree(p->sd.cols);
+    p->sd = sddmm_state();
+}
+
 // C's place behind B in that scratch: the next 256-byte boundary (the families' vector accesses)
 size_t linear_c_offset(uint64_t K, uint32_t N, size_t e) { return ((size_t)K * N * e + 255) / 256 * 256; }
 
@@ -338,6 +379,49 @@ void launch_linear_tiles(gs_plan *p, int replica, linear_ks_state &l, const void
     l.last = 0;  // (unknown if the launch throws)
     gs::launch_linear_fused(p->st, replica, X, Y, n, s, e, (float *)l.buf, arrivals);
     l.last = T;
+}
+
+// gs_sddmm's plan: on the device, at a 16-bit dtype, with a pattern; returns the dtype
+int sddmm_plan_dtype(gs_plan *p) {
+    auto ks = kernel_states(p);
+    for (gs::plan_state *s : ks) GS_CHECK(s->uploaded, "plan is not on the device");
+    const int dtype = ks.front()->dev.dtype;
+    GS_CHECK(dtype == gs::kF16 || dtype == gs::kBF16, "gs_sddmm runs f16 and bf16 plans (an f32 plan has no sampled product)");
+    GS_CHECK(!p->pat.rp.empty(), "the plan holds no pattern (read from a plan file whose pipeline padded or divided the matrix, or past 32-bit offsets)");
+    return dtype;
+}
+
+// the pattern arrays on the plan's device: uploaded once per plan, by the first gs_sddmm or by
+// gs_plan_sddmm_prepare, freed with the plan.  Synchronous, as ensure_csr: refused under stream capture
+void ensure_sddmm(gs_plan *p, hipStream_t stream, bool may_capture) {
+    if (p->sd.rp) return;
+    if (may_capture && capturing(stream))
+        throw gs::gs_error("gs_sddmm: the pattern is uploaded on first use: call gs_plan_sddmm_prepare before capturing", -2);
+    const int device = kernel_states(p).front()->dev.device;
+    const gs::sddmm_pattern &pat = p->pat;
+    sddmm_state sd;
+    sd.device = device;
+    sd.col_bytes = gs::sddmm_col_bytes(p->st.K);
+    int prev = 0;
+    GS_HIP(hipGetDevice(&prev));
+    GS_HIP(hipSetDevice(device));
+    p->sd = sd;
+    try {
+        GS_HIP(hipMalloc((void **)&p->sd.rp, pat.rp.size() * sizeof(uint32_t)));
+        GS_HIP(hipMalloc(&p->sd.cols, std::max<size_t>(1, pat.col.size()) * (size_t)sd.col_bytes));
+        GS_HIP(hipMemcpy(p->sd.rp, pat.rp.data(), pat.rp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (sd.col_bytes == 2) {
+            const std::vector<uint16_t> c16 = gs::sddmm_cols_u16(pat);
+            GS_HIP(hipMemcpy(p->sd.cols, c16.data(), c16.size() * 2, hipMemcpyHostToDevice));
+        } else {
+            GS_HIP(hipMemcpy(p->sd.cols, pat.col.data(), pat.col.size() * 4, hipMemcpyHostToDevice));
+        }
+    } catch (...) {  // nothing half-uploaded stays behind
+        free_sddmm(p);
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    GS_HIP(hipSetDevice(prev));
 }
 
 }  // namespace
@@ -702,6 +786,7 @@ int gs_plan_create_from_mtx(const char *path, int ones_values, gs_plan_t **out) 
         auto *p = new gs_plan;
         try {
             init_plan(p->st, gs::create_init_metadata_set_from_file(path, path, ones_values != 0));
+            snapshot_pattern(p);
         } catch (...) {
             delete p;
             throw;
@@ -717,6 +802,7 @@ int gs_plan_create_from_coo(uint64_t n_rows, uint64_t n_cols, uint64_t nnz, cons
         auto *p = new gs_plan;
         try {
             init_plan(p->st, gs::create_init_metadata_set_from_coo(n_rows, n_cols, nnz, row, col, val, "coo"));
+            snapshot_pattern(p);
         } catch (...) {
             delete p;
             throw;
@@ -874,6 +960,7 @@ int gs_plan_upload_ex(gs_plan_t *p, int dtype, int weights, const float *row_sca
         // parent-indexed sub-matrices, grouped by the row range they refer to
         free_groups(p);
         free_linear(p);  // (the dtype or the device may have changed)
+        free_sddmm(p);
         for (gs::plan_state *s : ks) {
             if (s->parent_row_base < 0) continue;
             auto g = std::find_if(p->groups.begin(), p->groups.end(), [&](const parent_group &x) {
@@ -1031,6 +1118,49 @@ int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, c
         gs::launch_tm_in(X, B, p->st.K, N, dtype, s);
         spmm_all(p, replica, B, C, N, s, nullptr);
         gs::launch_tm_out(C, Y, p->st.M, N, dtype, e, s);
+    });
+}
+
+int gs_plan_pattern(gs_plan_t *p, uint64_t *row, uint64_t *col, float *val, uint64_t cap, uint64_t *nnz) {
+    return guard([&] {
+        GS_CHECK(p && nnz, "null argument");
+        const gs::sddmm_pattern &pat = p->pat;
+        GS_CHECK(!pat.rp.empty(), "the plan holds no pattern (read from a plan file whose pipeline padded or divided the matrix, or past 32-bit offsets)");
+        *nnz = pat.nnz();
+        if (cap == 0) return;
+        GS_CHECK(cap >= pat.nnz() && row && col && val, "gs_plan_pattern: the buffers hold fewer than nnz entries");
+        for (uint64_t r = 0; r < pat.rows(); r++)
+            for (uint32_t e = pat.rp[r]; e < pat.rp[r + 1]; e++) row[e] = r;
+        std::copy(pat.col.begin(), pat.col.end(), col);
+        std::copy(pat.val.begin(), pat.val.end(), val);
+    });
+}
+
+int gs_sddmm_geometry(int *row_block, int *col_strip, int *token_chunk) {
+    return guard([&] {
+        GS_CHECK(row_block && col_strip && token_chunk, "null argument");
+        *row_block = 16 * gsk::kSddmmRT;
+        *col_strip = 16 * gsk::kSddmmCT;
+        *token_chunk = (int)gsk::kSddmmChunk;
+    });
+}
+
+int gs_plan_sddmm_prepare(gs_plan_t *p) {
+    return guard([&] {
+        GS_CHECK(p, "null plan");
+        sddmm_plan_dtype(p);
+        ensure_sddmm(p, nullptr, false);
+    });
+}
+
+int gs_sddmm(gs_plan_t *p, const void *G, const void *X, int n_tokens, float *out, gs_stream_t stream) {
+    return guard([&] {
+        // every check before the upload and the launch
+        GS_CHECK(p && G && X && out && n_tokens >= 1, "bad argument");
+        const int dtype = sddmm_plan_dtype(p);
+        hipStream_t s = (hipStream_t)stream;
+        ensure_sddmm(p, s, true);
+        gs::launch_sddmm(dtype, p->sd.col_bytes, G, X, p->sd.rp, p->sd.cols, out, (uint32_t)n_tokens, p->st.M, p->st.K, s);
     });
 }
 
@@ -1373,6 +1503,7 @@ int gs_plan_load(const char *path, gs_plan_t **out) {
                 st.parent_rows = ks.parent_rows;
                 st.cg->restore_compiled(ks.spec);
             }
+            snapshot_pattern(p);
         } catch (...) {
             delete p;
             throw;
@@ -1404,6 +1535,7 @@ void gs_plan_free(gs_plan_t *p) {
     try {
         free_groups(p);
         free_linear(p);
+        free_sddmm(p);
         gs::free_device(p->st);
         for (auto &kv : p->subs) gs::free_device(*kv.second);
     } catch (...) {

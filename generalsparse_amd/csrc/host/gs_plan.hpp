@@ -210,6 +210,11 @@ struct ks_group_item {
 };
 uint32_t ks_group_key(const plan_state &p, uint32_t N);  // 0: not groupable
 void launch_ks_group(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s);
+// sddmm_launch.hip: k_sddmm_tm (gs_sddmm).  out[e] = sum over t < n of G[t][row_e] * X[t][col_e] for the
+// entries of the CSR pattern rp (M + 1 u32) / cols (col_bytes 2: u16, 4: u32) in canonical order
+// (sddmm_layout.hpp); G: n x M, X: n x K of dtype (kF16 / kBF16), out: fp32.  Allocates nothing
+void launch_sddmm(int dtype, int col_bytes, const void *G, const void *X, const uint32_t *rp, const void *cols, float *out,
+                  uint32_t n, uint64_t M, uint64_t K, hipStream_t s);
 void launch_bm(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
 void debug_bm_timeline(const plan_state &p, const void *B, void *C, uint32_t N, hipStream_t s, uint64_t *host,
                        size_t n_host);

@@ -3,11 +3,61 @@
     layer = SparseLinear.from_dense(weight, bias, tokens=32, activation="relu")   # weight: (out, in), pruned
     y = layer(x)                                                                     # x: (..., in) -> (..., out)
 
-Inference only: the engine has no backward pass."""
+Inference only by default.  Gradients are opt-in:
+
+    layer = SparseLinear.from_dense(weight, bias, grad="input")   # a frozen sparse layer gradients flow through
+    layer = SparseLinear.from_dense(weight, bias, grad="all")     # ... and layer.values / layer.bias are trained
+    loss(layer(x)).backward(); optimizer.step(); layer.sync_values()
+
+The backward pass is the engine's own: grad_x = Plan.linear of the transposed weight (a second plan, so
+the weight is resident twice), grad_values = Plan.sddmm (k_sddmm_tm, the product sampled at the
+weight's non-zeros, in float32).  Once differentiable; FP8-weight layers stay inference only."""
 import numpy as np
 import torch
 
 from . import GS_W_FP8_E4M3, Plan, _check_activation, _dtype_code, _torch_dtype, _weights_code
+
+GRAD_MODES = (None, "input", "all")
+
+
+def _check_grad(grad):
+    """the gradient mode; checked before anything touches a device"""
+    if grad not in GRAD_MODES:
+        raise ValueError(f"grad must be None, 'input' or 'all', not {grad!r}")
+    return grad
+
+
+class _SparseLinearFn(torch.autograd.Function):
+    """y = layer's Plan.linear(x) -- the call and the bits of the inference path -- with the engine's
+    backward.  values and bias are inputs only so that autograd routes their gradients: the forward runs
+    on the values the plan holds (SparseLinear.sync_values)."""
+
+    @staticmethod
+    def forward(ctx, x, residual, values, bias, layer):
+        plan, act = layer.plan, layer.activation
+        b = bias.detach() if bias is not None else None
+        y = plan.linear(x, bias=b, activation=act, residual=residual)
+        mask = None
+        if act == "relu":
+            # the activation's own output decides the mask; with a residual fused after it that output
+            # is not y: it is computed once more without the residual, never from y - residual
+            mask = (y if residual is None else plan.linear(x, bias=b, activation=act)) > 0
+        ctx.layer, ctx.plan = layer, plan
+        ctx.save_for_backward(x, mask)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, mask = ctx.saved_tensors
+        need_x, need_res, need_val, need_bias = ctx.needs_input_grad[:4]
+        gy = gy.contiguous()
+        g = gy if mask is None else torch.where(mask, gy, torch.zeros((), dtype=gy.dtype, device=gy.device))
+        grad_x = ctx.layer.prepare_backward().plan_T.linear(g) if need_x else None
+        grad_values = ctx.plan.sddmm(g, x) if need_val else None
+        grad_bias = g.float().sum(0) if need_bias else None
+        # (the residual's gradient is a copy: autograd may keep a returned tensor as .grad and add to it in place)
+        return grad_x, (gy.clone() if need_res else None), grad_values, grad_bias, None
 
 
 class SparseLinear(torch.nn.Module):
@@ -18,33 +68,62 @@ class SparseLinear(torch.nn.Module):
     tokens is the width the plan's tiles are built for, not a batch size the layer is tied to: a
     layer built with tokens=32 (a k_mfma_ks plan) runs the one kernel k_mfma_ks_tm at any token
     count -- 8 tokens of a decode step, 100 of a prefill chunk -- on ceil(n / 32) token tiles, and a
-    token's output has the same bits in every such call (Plan.linear_fused, Plan.linear_launches)."""
+    token's output has the same bits in every such call (Plan.linear_fused, Plan.linear_launches).
 
-    def __init__(self, plan, bias=None, activation=None):
+    grad: None -- inference only, an input that requires grad is refused; "input" -- gradients flow to
+    x, and to residual when given; "all" -- also to layer.values, a float32 Parameter of the plan's nnz
+    stored values in Plan.pattern()'s order (np.nonzero's for from_dense), and to layer.bias, a float32
+    Parameter in this mode only.  The forward under grad is the same Plan.linear call with the same
+    bits (ReLU with a residual runs it a second time, without the residual, for the mask).  The
+    backward needs plan_T, a plan of the transposed weight built from the pattern with the layer's
+    pipeline, token width, dtype and device -- on the first backward, or by prepare_backward() -- which
+    DOUBLES the resident weight.  The forward keeps running on the values the plan was built from:
+    after an optimizer step sync_values() rebuilds both plans from layer.values (host side, slow).
+    A layer with FP8 weights is inference only: asking it for grad raises."""
+
+    def __init__(self, plan, bias=None, activation=None, grad=None):
         super().__init__()
         _check_activation(activation)  # before anything touches a device
-        self.plan, self.activation = plan, activation
+        _check_grad(grad)
+        self.plan, self.activation, self.grad = plan, activation, grad
+        self.plan_T = None
         info = plan.info()
+        if grad is not None and info["weights"] == GS_W_FP8_E4M3:
+            raise ValueError("a SparseLinear with FP8 weights is inference only: the transposed product would run on "
+                             "other weights than the forward did")
         self.in_features, self.out_features = int(info["cols"]), int(info["rows"])
         self.tokens = int(info["lds_n"]) or None  # the width the plan's tiles were built for
+        # how plan_T (and sync_values' plans) are built; from_dense records its own arguments
+        self._build = {"tokens": self.tokens or 32, "dtype": info["dtype"], "pipeline": ("block_total", 40, 1),
+                       "device": getattr(plan, "_device", 0), "rebuild": False}
         if bias is not None:
             bias = torch.as_tensor(bias).detach().to(torch.float32).reshape(-1).contiguous()
             if bias.numel() != self.out_features:
                 raise ValueError(f"bias must hold {self.out_features} values (one per output feature)")
-        self.register_buffer("bias", bias)
+        if grad == "all":
+            self.register_parameter("bias", torch.nn.Parameter(bias) if bias is not None else None)
+            values = torch.from_numpy(plan.values())
+            if info["replicas"]:
+                values = values.to(torch.device("cuda", self._build["device"]))
+            self.values = torch.nn.Parameter(values)
+        else:
+            self.register_buffer("bias", bias)
 
     @classmethod
     def from_dense(cls, weight, bias=None, *, tokens=32, dtype="f16", pipeline=("block_total", 40, 1), activation=None,
-                   device=0, upload=True, weights=None, row_scale=None):
+                   device=0, upload=True, weights=None, row_scale=None, grad=None):
         """the plan from the non-zeros of a pruned (out, in) weight: from_coo, run_pipeline at
         N = tokens, compile, upload (upload=False stops before the device: the plan can be inspected,
         the module cannot run).  tokens: the tile width (17 .. 32 for the one-kernel path), whatever
         token counts forward will see.  weights="fp8" (with row_scale: one scale per output feature, or
         the default power-of-two rule): the weight's values as e4m3 codes, Plan.upload's weight-only
-        quantisation -- activations, bias and output stay `dtype`, which must be f16"""
+        quantisation -- activations, bias and output stay `dtype`, which must be f16; not with grad.
+        grad: the constructor's"""
         _check_activation(activation)
-        _dtype_code(dtype)
-        _weights_code(weights)
+        _check_grad(grad)
+        code, wcode = _dtype_code(dtype), _weights_code(weights)
+        if grad is not None and wcode == GS_W_FP8_E4M3:
+            raise ValueError("a SparseLinear with FP8 weights is inference only: grad must be None")
         w = torch.as_tensor(weight).detach().to("cpu", torch.float32).numpy()
         if w.ndim != 2:
             raise ValueError("weight must be (out_features, in_features)")
@@ -56,14 +135,55 @@ class SparseLinear(torch.nn.Module):
             plan.upload(dtype, int(device), weights=weights, row_scale=row_scale)
             if bias is not None:
                 bias = torch.as_tensor(bias).detach().to(torch.device("cuda", int(device)), torch.float32)
-        layer = cls(plan, bias, activation)
+        layer = cls(plan, bias, activation, grad)
         layer.tokens = int(tokens)
+        layer._build = {"tokens": int(tokens), "dtype": code, "pipeline": (name, int(p0), int(p1)), "device": int(device),
+                        "rebuild": True}
         return layer
+
+    # ------------------------------------------------------------- backward
+    def _plan_of(self, n_rows, n_cols, row, col, val):
+        b = self._build
+        name, p0, p1 = b["pipeline"]
+        plan = Plan.from_coo(n_rows, n_cols, row, col, val).run_pipeline(name, b["tokens"], p0, p1).compile()
+        return plan.upload(b["dtype"], b["device"])
+
+    def _current_values(self):
+        if self.grad == "all":
+            return self.values.detach().to("cpu", torch.float32).numpy()
+        return self.plan.values()
+
+    def prepare_backward(self):
+        """builds plan_T, the plan of the transposed weight that grad_x runs on, now rather than in the
+        first backward (host-side plan building and an upload; the weight is then resident twice)"""
+        if self.grad is None:
+            raise RuntimeError("SparseLinear(grad=None) is inference only: build it with grad='input' or 'all'")
+        if self.plan_T is None:
+            row, col = self.plan.pattern()
+            val = self._current_values()
+            order = np.lexsort((row, col))  # by column, then row: the transposed weight, row-major
+            self.plan_T = self._plan_of(self.in_features, self.out_features, col[order], row[order], val[order])
+        return self
+
+    def sync_values(self):
+        """rebuilds the plan (and plan_T, if built) from the pattern and the current layer.values, so that
+        an optimizer step reaches the forward.  The slow, host-side way: two plan builds and uploads.  For
+        from_dense layers with grad="all", which remember how their plan was built."""
+        if self.grad != "all" or not self._build["rebuild"]:
+            raise RuntimeError("sync_values is for SparseLinear.from_dense(..., grad='all') layers")
+        row, col = self.plan.pattern()
+        val = np.ascontiguousarray(self._current_values())
+        had_T = self.plan_T is not None
+        self.plan = self._plan_of(self.out_features, self.in_features, row, col, val)
+        self.plan_T = None
+        if had_T:
+            self.prepare_backward()
+        return self
 
     def forward(self, x, residual=None):
         """x: (..., in_features) of the plan's dtype on its device -> (..., out_features); the leading
         dimensions are flattened into the token count.  residual: (..., out_features), added last."""
-        if torch.is_grad_enabled() and x.requires_grad:
+        if self.grad is None and torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("SparseLinear is inference only (no backward pass): run it under torch.no_grad() "
                                "or on a tensor that does not require grad")
         if x.dim() < 1 or x.shape[-1] != self.in_features:
@@ -78,7 +198,13 @@ class SparseLinear(torch.nn.Module):
             residual = residual.reshape(-1, self.out_features)
             if not residual.is_contiguous():
                 residual = residual.contiguous()
-        y = self.plan.linear(x2, bias=self.bias, activation=self.activation, residual=residual)
+        if self.grad is not None and torch.is_grad_enabled():
+            values = self.values if self.grad == "all" else None
+            if any(t is not None and t.requires_grad for t in (x2, residual, values, self.bias)):
+                y = _SparseLinearFn.apply(x2, residual, values, self.bias, self)
+                return y.reshape(lead + (self.out_features,))
+        bias = self.bias.detach() if isinstance(self.bias, torch.nn.Parameter) else self.bias
+        y = self.plan.linear(x2, bias=bias, activation=self.activation, residual=residual)
         return y.reshape(lead + (self.out_features,))
 
     def extra_repr(self):
@@ -86,6 +212,8 @@ class SparseLinear(torch.nn.Module):
         kernel = info["device_kernel"] or info["kernel_name"]
         s = f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
             f"activation={self.activation!r}, kernel={kernel}"
+        if self.grad is not None:
+            s += f", grad={self.grad!r}"
         if self.tokens:
             s += f", linear_fused({self.tokens})={self.plan.linear_fused(self.tokens)}"
         if info["replicas"]:

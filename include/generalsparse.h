@@ -221,6 +221,32 @@ int gs_plan_linear_launches(gs_plan_t *p, int n_tokens, int *tiles, int cap);
  * needs no state: only the limit of 16383 tiles per launch splits a call) */
 int gs_linear_tile_split(uint64_t row_blocks, int k_ranges, int row_tiles, int n_tokens, long long ws_kb,
                          unsigned long long *tile_bytes, int *tiles, int cap);
+/* The plan's pattern in one canonical order, host only: by original row, then by column; stored duplicates
+ * of one coordinate are adjacent and keep their input order (for a row-major dense weight: the order of
+ * its non-zeros).  row / col / val receive the original row, the column and the fp32 value the plan
+ * holds of every entry; *nnz their number.  cap == 0 only returns *nnz; a smaller cap than nnz is
+ * refused.  The pattern is taken when the plan is created, so it is the same after any pipeline (a
+ * sorted plan's row order, interleaved storage and padding entries never reach it) and needs no upload.
+ * A plan read by gs_plan_load has it unless its pipeline padded or divided the matrix (GS_ERR). */
+int gs_plan_pattern(gs_plan_t *p, uint64_t *row, uint64_t *col, float *val, uint64_t cap, uint64_t *nnz);
+/* The sampled product on token-major operands (the weight gradient of gs_linear):
+ *   out[e] = sum over t < n_tokens of G[t][row_e] * X[t][col_e],  e = 0 .. nnz - 1 in gs_plan_pattern's order.
+ * G: n_tokens x M and X: n_tokens x K, row-major, one row per token, exactly as gs_linear gives Y and
+ * takes X, in the plan's dtype; out: nnz fp32 values (the sums are not rounded to 16 bits).  One kernel,
+ * k_sddmm_tm, whatever the plan's kernel family: it reads only the pattern.  fp32 accumulation over the
+ * tokens in one fixed order, no atomics: out[e] depends on column row_e of G, column col_e of X and
+ * n_tokens only, and two calls give the same bits.  A non-finite value makes the entries of its row of
+ * the pattern (G) or of its column (X) NaN, and no others.
+ * The plan must be on the device (for the dtype and the device) at GS_F16 or GS_BF16; an FP8-weight plan
+ * is an f16 plan here.  A GS_F32 plan is refused (GS_ERR).  The pattern arrays (M + 1 offsets, nnz columns
+ * of 2 bytes where K <= 65536, else 4) go to the device once per plan -- by the first call, or by
+ * gs_plan_sddmm_prepare -- and are freed with the plan; the upload is synchronous, so a first call inside
+ * stream capture is refused unless gs_plan_sddmm_prepare ran before.  Every argument is checked before
+ * anything is uploaded or launched.  The caller guarantees the extents behind the raw pointers. */
+int gs_sddmm(gs_plan_t *p, const void *G, const void *X, int n_tokens, float *out, gs_stream_t stream);
+int gs_plan_sddmm_prepare(gs_plan_t *p);
+/* k_sddmm_tm's tiling: output features per workgroup, input features per wave strip, tokens per chunk */
+int gs_sddmm_geometry(int *row_block, int *col_strip, int *token_chunk);
 /* `count` SpMMs enqueued back to back from native code, call i using replica
  * (first + i) % replicas with B_ptrs / C_ptrs entry (first + i) % n_ptrs
  * (bench rotation without a host round trip per launch) */
