@@ -176,8 +176,9 @@ void launch_gather(const plan_state &p, const device_arrays &a, const void *B, v
 // ks_launch.hip: k_mfma_ks (K-split, wave-autonomous matrix-core row blocks)
 void launch_ks(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
                const gsk::epilogue &epi = gsk::epilogue_identity());
-// ks_w8_launch.hip / ks_tm_w8_launch.hip: the FP8-weight forms (k_mfma_ks_w8, k_mfma_ks_tm with VB = 8) behind
-// launch_ks and launch_linear_fused, for plans uploaded with kWFp8 (same arguments, plus the replica's scales)
+// the FP8-weight forms behind launch_ks and launch_linear_fused, for plans uploaded with kWFp8 (same arguments,
+// plus the replica's scales): k_mfma_ks_w8 (ks_w8_launch.hip) and k_mfma_ks_tm with VB = 8 (ks_tm_launch.hip's
+// object ks_tm_w8_launch.o)
 void launch_ks_w8(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
                   const gsk::epilogue &epi);
 void launch_ks_tm_w8(const plan_state &p, const device_arrays &a, const void *X, void *Y, uint32_t N, hipStream_t s,

@@ -809,15 +809,11 @@ void combine_parts(const void *const *parts, const uint32_t *rows, uint32_t n, v
     const uint64_t total = P * N;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
     if (blocks == 0) return;
-    if (dtype == kF32)
-        hipLaunchKernelGGL(gsk::k_combine_parts<float>, dim3(blocks), dim3(256), 0, stream,
-                           (const float *const *)parts, rows, n, (float *)C + row0 * N, total, N);
-    else if (dtype == kBF16)
-        hipLaunchKernelGGL(gsk::k_combine_parts<gsk::bf16>, dim3(blocks), dim3(256), 0, stream,
-                           (const gsk::bf16 *const *)parts, rows, n, (gsk::bf16 *)C + row0 * N, total, N);
-    else
-        hipLaunchKernelGGL(gsk::k_combine_parts<gsk::f16>, dim3(blocks), dim3(256), 0, stream,
-                           (const gsk::f16 *const *)parts, rows, n, (gsk::f16 *)C + row0 * N, total, N);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gsk::k_combine_parts<T>, dim3(blocks), dim3(256), 0, stream, (const T *const *)parts, rows, n,
+                           (T *)C + row0 * N, total, N);
+    });
     HIP_OK(hipGetLastError());
 }
 
@@ -844,12 +840,10 @@ void launch_epilogue(void *C, uint64_t rows, uint32_t N, int dtype, const gsk::e
     const uint32_t vec = ((size_t)N * e) % 16 == 0 && (uintptr_t)C % 16 == 0 && (uintptr_t)epi.residual % 16 == 0;
     const uint64_t items = vec ? total / (16 / e) : total;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 255) / 256, 4096);
-    if (dtype == kF32)
-        hipLaunchKernelGGL(gsk::k_epilogue<float>, dim3(blocks), dim3(256), 0, stream, (float *)C, epi, total, N, vec);
-    else if (dtype == kBF16)
-        hipLaunchKernelGGL(gsk::k_epilogue<gsk::bf16>, dim3(blocks), dim3(256), 0, stream, (gsk::bf16 *)C, epi, total, N, vec);
-    else
-        hipLaunchKernelGGL(gsk::k_epilogue<gsk::f16>, dim3(blocks), dim3(256), 0, stream, (gsk::f16 *)C, epi, total, N, vec);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gsk::k_epilogue<T>, dim3(blocks), dim3(256), 0, stream, (T *)C, epi, total, N, vec);
+    });
     HIP_OK(hipGetLastError());
 }
 
@@ -866,14 +860,10 @@ void launch_tm_in(const void *X, void *B, uint64_t K, uint32_t N, int dtype, hip
 void launch_tm_out(const void *C, void *Y, uint64_t M, uint32_t N, int dtype, const gsk::epilogue &epi, hipStream_t stream) {
     GS_CHECK(M >= 1 && N >= 1 && M < (1ull << 32) && (N + 31) / 32 <= 65535u, "launch_tm_out: bad sizes");
     const dim3 grid((uint32_t)((M + 31) / 32), (N + 31) / 32);
-    if (dtype == kF32)
-        hipLaunchKernelGGL(gsk::k_tm_out<float>, grid, dim3(256), 0, stream, (const float *)C, (float *)Y, epi, (uint32_t)M, N);
-    else if (dtype == kBF16)
-        hipLaunchKernelGGL(gsk::k_tm_out<gsk::bf16>, grid, dim3(256), 0, stream, (const gsk::bf16 *)C, (gsk::bf16 *)Y, epi,
-                           (uint32_t)M, N);
-    else
-        hipLaunchKernelGGL(gsk::k_tm_out<gsk::f16>, grid, dim3(256), 0, stream, (const gsk::f16 *)C, (gsk::f16 *)Y, epi,
-                           (uint32_t)M, N);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gsk::k_tm_out<T>, grid, dim3(256), 0, stream, (const T *)C, (T *)Y, epi, (uint32_t)M, N);
+    });
     HIP_OK(hipGetLastError());
 }
 

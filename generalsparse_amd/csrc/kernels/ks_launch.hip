@@ -1,14 +1,14 @@
 // ks_launch.hip -- launches of k_mfma_ks (hip_code/mfma_ks.hpp), the K-split,
 // B-stationary matrix-core kernel for tall BMTB row blocks.  Its own translation unit
 // so the kernel's instantiations build in parallel with device_plan.hip.
-// Built twice (Makefile): ks_launch.o holds the fp16 instantiations and every entry point,
-// ks_launch_bf16.o (-DGS_KS_BF16_OBJECT) only the bf16 twins behind launch_ks_bf16 /
-// launch_ks_group_bf16, so the two sets of kernels compile in parallel.
+// Built twice (Makefile; GS_KS_OBJECT, ks_dispatch.hpp): ks_launch.o holds the fp16 instantiations and
+// every entry point, ks_launch_bf16.o only the bf16 twins behind launch_ks_bf16 / launch_ks_group_bf16, so
+// the two sets of kernels compile in parallel.
 #include "../hip_code/mfma_ks.hpp"
 #ifdef GS_EXPERIMENTS
 #include "../hip_code/mfma_bm_exp.hpp"
 #endif
-#include "launch_common.hpp"
+#include "ks_dispatch.hpp"
 
 #include <cstring>
 
@@ -16,16 +16,9 @@ namespace gs {
 
 namespace {
 
-// k_mfma_ks's prio argument: KS_PRIO in bits 0..1; bit 4 (experiments build) forces the K-split
-// combine's timeout path (KS_FORCE_TIMEOUT, the test of the device error word)
-uint32_t ks_prio_arg() {
-    const config_t c = get_config();
-    return (uint32_t)(c.KS_PRIO & 3) | (c.KS_FORCE_TIMEOUT ? 16u : 0u);
-}
-
 // ET: the plan's 16-bit element type (gsk::f16, or gsk::bf16 for GS_BF16 plans).  The bf16 twins are
-// built for the release instantiations only (8 waves, apart layout, 16-bit positions, KS_NT 0 / 1):
-// the experiments-build variants below stay fp16 kernels and refuse a bf16 plan
+// built for the release instantiations only (ks_release_layout): the experiments-build variants and
+// KS_WPOS below stay fp16 kernels and refuse a bf16 plan
 template <int CT, int RT, int MAXG, bool STAMPS = false, int W = (int)kKsWaves, class ET = gsk::f16>
 void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s,
                  uint64_t *stamps = nullptr, const gsk::epilogue &epi = gsk::epilogue_identity()) {
@@ -34,11 +27,19 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
     GS_CHECK(d.weights == kWNative, "k_mfma_ks reads 16-bit values: a plan with FP8 weights runs k_mfma_ks_w8 (launch_ks)");
     if constexpr (!F16) {
         static_assert(W == (int)kKsWaves && !STAMPS, "bf16: the release instantiations only");
-        GS_CHECK(d.waves == kKsWaves && !d.ks_p8 && d.ks_ap && !d.ks_persist,
-                 "k_mfma_ks at bf16 is built for 8 waves, 16-bit positions and the apart LDS layout: the experiments "
-                 "variants (KS_WAVES, KS_POS8, KS_APART = 0, KS_PERSIST) are fp16 kernels");
-        GS_CHECK(!d.ks_wp, "k_mfma_ks at bf16 is built for 16-bit positions: KS_WPOS is an fp16 layout");
+        GS_CHECK(ks_release_layout(d),
+                 "k_mfma_ks at bf16 is built for 8 waves, 16-bit positions and the apart LDS layout: KS_WPOS and the "
+                 "experiments variants (KS_WAVES, KS_POS8, KS_APART = 0, KS_PERSIST) are fp16 kernels");
     }
+    // a launch of the k_mfma_ks signature on the plan's static grid
+    auto run = [&](auto k, uint32_t threads, uint32_t prio, const uint8_t *tW) {
+        grant_lds(d.device, k, d.lds_bytes);
+        const uint32_t nwg = (uint32_t)d.n_rows_aux * d.ksplit;
+        hipLaunchKernelGGL(k, dim3(nwg, ks_col_tiles_ct(N, CT)), dim3(threads), d.lds_bytes, s, a.t0, (const gsk::u32x4 *)a.tcol,
+                           (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C, (uint32_t)p.K, N, d.ksplit, d.ks_ns, nwg,
+                           (uint32_t)d.row_base, a.ws, a.t2, stamps, prio, tW, epi);
+        HIP_OK(hipGetLastError());
+    };
 #ifdef GS_EXPERIMENTS
     // KS_WAVES = 16 (fixed at upload): every instantiation spills (128 VGPRs at 4 waves per
     // SIMD; C2 48-98 us against 14-30 us with 8 waves, profiles/r04a), experiments build only
@@ -64,12 +65,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
             GS_CHECK(!d.ks_gh && !d.ks_nt && !d.ks_wp, "GS_KS_DEPTH: upload the plan with KS_HEAD = 0, KS_NT = 0 and u16 positions");
             auto kd = dep == 1 ? gsk::k_mfma_ks<CT, RT, W, 1, MAXG, false>
                                : dep == 3 ? gsk::k_mfma_ks<CT, RT, W, 3, MAXG, false> : gsk::k_mfma_ks<CT, RT, W, 4, MAXG, false>;
-            grant_lds(d.device, kd, d.lds_bytes);
-            hipLaunchKernelGGL(kd, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(64 * W), d.lds_bytes, s,
-                               a.t0, (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C,
-                               (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit, (uint32_t)d.row_base,
-                               a.ws, a.t2, stamps, ks_prio_arg(), (const uint8_t *)nullptr, epi);
-            HIP_OK(hipGetLastError());
+            run(kd, 64 * W, ks_prio_word(d) & kKsPrioFlags, nullptr);  // (no head steps: ks_gh is 0, checked above)
             return;
         }
     }
@@ -83,12 +79,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
                 auto k4 = d.ks_p8 ? gsk::k_mfma_ks<CT, RT, 4, (int)kKsDepth, MAXG, false, false, gsk::kKsPos8>
                                   : gsk::k_mfma_ks<CT, RT, 4, (int)kKsDepth, MAXG, false, false, gsk::kKsPosU16>;
                 GS_CHECK(gsk::ks_lds_bytes(CT, RT, 4, false) <= d.lds_bytes, "k_mfma_ks: LDS size disagrees with the upload");
-                grant_lds(d.device, k4, d.lds_bytes);
-                hipLaunchKernelGGL(k4, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(256), d.lds_bytes,
-                                   s, a.t0, (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B,
-                                   C, (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit,
-                                   (uint32_t)d.row_base, a.ws, a.t2, stamps, ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)nullptr, epi);
-                HIP_OK(hipGetLastError());
+                run(k4, 256, ks_prio_word(d), nullptr);
                 return;
             } else {
                 throw gs_error("k_mfma_ks with 4 waves is built for N = 32");
@@ -147,8 +138,7 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
             const uint32_t nunits = (uint32_t)d.n_rows_aux * d.ksplit;
             hipLaunchKernelGGL(kp, dim3(std::min(d.ks_persist, nunits)), dim3(64 * W), d.lds_bytes, s, a.t0,
                                (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C,
-                               (uint32_t)p.K, N, d.ksplit, d.ks_ns, nunits, (uint32_t)d.row_base, a.ws, a.t2,
-                               ks_prio_arg() | (d.ks_gh << 8), a.t3);
+                               (uint32_t)p.K, N, d.ksplit, d.ks_ns, nunits, (uint32_t)d.row_base, a.ws, a.t2, ks_prio_word(d), a.t3);
             HIP_OK(hipGetLastError());
             return;
         } else {
@@ -160,59 +150,42 @@ void launch_ks_k(const plan_state &p, const device_arrays &a, const ET *B, ET *C
 #endif
     // the LDS this instantiation needs at the plan's range width, against what the upload sized
     GS_CHECK(gsk::ks_lds_bytes(CT, RT, W, d.ks_ap) <= d.lds_bytes, "k_mfma_ks: LDS size disagrees with the upload");
-    grant_lds(d.device, kern, d.lds_bytes);
-    hipLaunchKernelGGL(kern, dim3((uint32_t)d.n_rows_aux * d.ksplit, ks_col_tiles_ct(N, CT)), dim3(64 * W), d.lds_bytes, s, a.t0,
-                       (const gsk::u32x4 *)a.tcol, (const gsk::u32x4 *)a.tval, (const gsk::u32x2 *)a.t1, B, C,
-                       (uint32_t)p.K, N, d.ksplit, d.ks_ns, (uint32_t)d.n_rows_aux * d.ksplit, (uint32_t)d.row_base, a.ws, a.t2, stamps,
-                       ks_prio_arg() | (d.ks_gh << 8), (const uint8_t *)a.tw, epi);
-    HIP_OK(hipGetLastError());
+    run(kern, 64 * W, ks_prio_word(d), (const uint8_t *)a.tw);
 }
 
-template <int CT, int RT, class ET>
-void launch_ks_rt(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s,
+// the plan's (CT, RT, MAXG) as template arguments.  CT: 16-column tiles per workgroup, ks_col_tiles_ct(N, CT)
+// workgroups across N; RT: 16-row tiles per row block (the upload builds RT >= 2); MAXG: entry groups per
+// lane per k-step, 4 for any other count
+template <class ET>
+void launch_ks_et(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
                   const gsk::epilogue &epi) {
-    if constexpr (CT == 8) {  // 128-column tiles: only the (RT, MAXG) pairs that do not spill (ks_ct8_fits)
-        GS_CHECK(ks_ct8_fits(RT, p.dev.seg_cap), "k_mfma_ks: 128-column tile instantiation not built for this plan");
-        if constexpr (RT == 2) {
-            switch (p.dev.seg_cap) {
-                case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
-                case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
-                default: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
+    const device_plan &d = p.dev;
+    for_value<1, 2, 4, 8>(d.ks_ctw, "k_mfma_ks: bad column tile count", [&](auto ct) {
+        constexpr int CT = decltype(ct)::value;
+        constexpr const char *rt_err = CT == 8 ? "k_mfma_ks: 128-column tiles take row blocks of up to 48 rows"
+                                               : "k_mfma_ks: row tiles outside 2..8 (6..8 for N <= 32)";
+        for_value<2, 3, 4, 5, 6, 7, 8>(d.maxr, rt_err, [&](auto rt) {
+            constexpr int RT = decltype(rt)::value;
+            auto run = [&](auto maxg) {
+                launch_ks_k<CT, RT, decltype(maxg)::value, false, (int)kKsWaves, ET>(p, a, (const ET *)B, (ET *)C, N, s, nullptr, epi);
+            };
+            if constexpr (CT == 8) {
+                // 128 columns per workgroup: row blocks of up to 48 rows (ks_ct_rt), and only the (RT, MAXG)
+                // pairs that do not spill (ks_ct8_fits): MAXG up to 3 at RT 2, 1 at RT 3
+                if constexpr (RT > 3) {
+                    throw gs_error(rt_err);
+                } else {
+                    GS_CHECK(ks_ct8_fits(RT, d.seg_cap), "k_mfma_ks: 128-column tile instantiation not built for this plan");
+                    if constexpr (RT == 2) for_value<1, 2, 3>(d.seg_cap, nullptr, run);
+                    else run(std::integral_constant<int, 1>{});
+                }
+            } else if constexpr (CT > 2 && RT > 5) {  // RT 6..8 are built for N <= 32 (CT <= 2)
+                throw gs_error(rt_err);
+            } else {
+                for_value<1, 2, 3, 4>(d.seg_cap, nullptr, run);
             }
-        } else {
-            launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi);
-        }
-    } else {
-        switch (p.dev.seg_cap) {  // MAXG: entry groups per lane per k-step
-            case 1: launch_ks_k<CT, RT, 1, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
-            case 2: launch_ks_k<CT, RT, 2, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
-            case 3: launch_ks_k<CT, RT, 3, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
-            default: launch_ks_k<CT, RT, 4, false, (int)kKsWaves, ET>(p, a, B, C, N, s, nullptr, epi); break;
-        }
-    }
-}
-
-template <int CT, class ET>
-void launch_ks_ct(const plan_state &p, const device_arrays &a, const ET *B, ET *C, uint32_t N, hipStream_t s,
-                  const gsk::epilogue &epi) {
-    if constexpr (CT == 8) {  // 128 columns per workgroup: row blocks of up to 48 rows (ks_ct_rt)
-        switch (p.dev.maxr) {
-            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s, epi); return;
-            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s, epi); return;
-            default: throw gs_error("k_mfma_ks: 128-column tiles take row blocks of up to 48 rows");
-        }
-    } else {
-        switch (p.dev.maxr) {  // RT: 16-row tiles per row block (the upload builds RT >= 2)
-            case 2: launch_ks_rt<CT, 2, ET>(p, a, B, C, N, s, epi); break;
-            case 3: launch_ks_rt<CT, 3, ET>(p, a, B, C, N, s, epi); break;
-            case 4: launch_ks_rt<CT, 4, ET>(p, a, B, C, N, s, epi); break;
-            case 5: launch_ks_rt<CT, 5, ET>(p, a, B, C, N, s, epi); break;
-            case 6: if constexpr (CT <= 2) { launch_ks_rt<CT, 6, ET>(p, a, B, C, N, s, epi); break; } [[fallthrough]];
-            case 7: if constexpr (CT <= 2) { launch_ks_rt<CT, 7, ET>(p, a, B, C, N, s, epi); break; } [[fallthrough]];
-            case 8: if constexpr (CT <= 2) { launch_ks_rt<CT, 8, ET>(p, a, B, C, N, s, epi); break; } [[fallthrough]];
-            default: throw gs_error("k_mfma_ks: row tiles outside 2..8 (6..8 for N <= 32)");
-        }
-    }
+        });
+    });
 }
 
 #ifdef GS_EXPERIMENTS
@@ -259,52 +232,33 @@ void launch_kb_k(const plan_state &p, const device_arrays &a, const gsk::f16 *B,
     const uint32_t nwg = (uint32_t)d.n_rows_aux * d.ksplit;
     hipLaunchKernelGGL(kern, dim3(nwg, ks_col_tiles(N)), dim3(64 * kKsWaves), d.lds_bytes, s, a.t0, (const uint2 *)a.tcol,
                        a.t1, (const gsk::f16 *)a.tval, B, C, (uint32_t)p.K, N, d.ksplit, d.ks_ns, nwg,
-                       (uint32_t)d.row_base, a.ws, a.t2, nullptr, ks_prio_arg());
+                       (uint32_t)d.row_base, a.ws, a.t2, nullptr, ks_prio_word(d) & kKsPrioFlags);  // (the bitmap layout has no head steps)
     HIP_OK(hipGetLastError());
-}
-
-template <int CT, int RT>
-void launch_bm_rt(const plan_state &p, const device_arrays &a, const gsk::f16 *B, gsk::f16 *C, uint32_t N, hipStream_t s) {
-    if (p.dev.bmkb) {
-        switch (p.dev.seg_cap) {  // NVB
-            case 1: launch_kb_k<CT, RT, 1>(p, a, B, C, N, s); break;
-            case 2: launch_kb_k<CT, RT, 2>(p, a, B, C, N, s); break;
-            default: launch_kb_k<CT, RT, 4>(p, a, B, C, N, s); break;
-        }
-    }
-    else if (p.dev.bm2) launch_bm2_k<CT, RT>(p, a, B, C, N, s);
-    else if (p.dev.waves == 4) launch_bm_k<CT, RT, 4>(p, a, B, C, N, s);
-    else launch_bm_k<CT, RT, 8>(p, a, B, C, N, s);
-}
-
-template <int CT>
-void launch_bm_ct(const plan_state &p, const device_arrays &a, const gsk::f16 *B, gsk::f16 *C, uint32_t N, hipStream_t s) {
-    switch (p.dev.maxr) {  // RT: 16-row tiles per row block
-        case 1: launch_bm_rt<CT, 1>(p, a, B, C, N, s); break;
-        case 2: launch_bm_rt<CT, 2>(p, a, B, C, N, s); break;
-        case 3: launch_bm_rt<CT, 3>(p, a, B, C, N, s); break;
-        case 4: launch_bm_rt<CT, 4>(p, a, B, C, N, s); break;
-        case 5: launch_bm_rt<CT, 5>(p, a, B, C, N, s); break;
-        case 6: launch_bm_rt<CT, 6>(p, a, B, C, N, s); break;
-        default: throw gs_error("k_mfma_bm: row tiles outside 1..6");
-    }
 }
 
 #endif  // GS_EXPERIMENTS
 
 }  // namespace
 
-#ifndef GS_KS_BF16_OBJECT
+#if GS_KS_OBJECT == GS_KS_F16
 #ifdef GS_EXPERIMENTS
 void launch_bm(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s) {
+    const device_plan &d = p.dev;
     const gsk::f16 *b = (const gsk::f16 *)B;
     gsk::f16 *c = (gsk::f16 *)C;
-    GS_CHECK(N == p.dev.lds_N, "k_mfma_bm runs the plan's dense width");
-    switch (ks_ct(N)) {
-        case 1: launch_bm_ct<1>(p, a, b, c, N, s); break;
-        case 2: launch_bm_ct<2>(p, a, b, c, N, s); break;
-        default: launch_bm_ct<4>(p, a, b, c, N, s); break;
-    }
+    GS_CHECK(N == d.lds_N, "k_mfma_bm runs the plan's dense width");
+    // CT: 16-column tiles per workgroup (4 for any wider N); RT: 16-row tiles per row block
+    for_value<1, 2, 4>(ks_ct(N), nullptr, [&](auto ct) {
+        constexpr int CT = decltype(ct)::value;
+        for_value<1, 2, 3, 4, 5, 6>(d.maxr, "k_mfma_bm: row tiles outside 1..6", [&](auto rt) {
+            constexpr int RT = decltype(rt)::value;
+            if (d.bmkb)  // NVB: 1, 2, else 4
+                for_value<1, 2, 4>(d.seg_cap, nullptr, [&](auto nvb) { launch_kb_k<CT, RT, decltype(nvb)::value>(p, a, b, c, N, s); });
+            else if (d.bm2) launch_bm2_k<CT, RT>(p, a, b, c, N, s);
+            else if (d.waves == 4) launch_bm_k<CT, RT, 4>(p, a, b, c, N, s);
+            else launch_bm_k<CT, RT, 8>(p, a, b, c, N, s);
+        });
+    });
 }
 
 #else
@@ -312,7 +266,7 @@ void launch_bm(const plan_state &, const device_arrays &, const void *, void *, 
     throw gs_error("k_mfma_bm is an experiments-build kernel (make -C generalsparse_amd/csrc exp)", -2);
 }
 #endif
-#endif  // !GS_KS_BF16_OBJECT
+#endif  // GS_KS_OBJECT == GS_KS_F16
 
 // ---- grouped launches (gs_spmm_batch): N = 32 (CT = 2), 8 waves, one instantiation per group
 namespace {
@@ -321,7 +275,7 @@ void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStre
     constexpr bool AP = W == (int)kKsWaves;
     constexpr bool F16 = std::is_same<ET, gsk::f16>::value;
     if constexpr (!F16)  // (ks_group_key admits bf16 plans of the release layout only)
-        GS_CHECK(it[0].p->dev.waves == kKsWaves && !it[0].p->dev.ks_p8, "k_mfma_ks_group at bf16: 8 waves, 16-bit positions");
+        GS_CHECK(ks_release_layout(it[0].p->dev), "k_mfma_ks_group at bf16: 8 waves, 16-bit positions");
 #ifdef GS_EXPERIMENTS
     if constexpr (F16 && W == (int)kKsWaves) {
         if (it[0].p->dev.waves == 4) {  // KS_WAVES = 4: 256-thread workgroups, overlapped LDS
@@ -385,50 +339,24 @@ void launch_ks_group_k(const std::vector<ks_group_item> &it, uint32_t N, hipStre
     args.begin[it.size()] = wg;
     args.n = (uint32_t)it.size();
     args.N = N;
-    args.pad[0] = ks_prio_arg();
+    args.pad[0] = ks_prio_word(it[0].p->dev) & kKsPrioFlags;  // (the head-step counts: each entry's pad0)
     grant_lds(it[0].p->dev.device, kern, lds);
     hipLaunchKernelGGL(kern, dim3(wg, ks_col_tiles(N)), dim3(64 * W), lds, s, args);
     HIP_OK(hipGetLastError());
 }
 
-template <int RT, class ET>
-void launch_ks_group_rt(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
-    switch (it[0].p->dev.seg_cap) {
-        case 1: launch_ks_group_k<RT, 1, (int)kKsWaves, ET>(it, N, s); break;
-        case 2: launch_ks_group_k<RT, 2, (int)kKsWaves, ET>(it, N, s); break;
-        case 3: launch_ks_group_k<RT, 3, (int)kKsWaves, ET>(it, N, s); break;
-        default: launch_ks_group_k<RT, 4, (int)kKsWaves, ET>(it, N, s); break;
-    }
-}
 template <class ET>
 void launch_ks_group_et(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s) {
-    switch (it[0].p->dev.maxr) {
-        case 2: launch_ks_group_rt<2, ET>(it, N, s); break;
-        case 3: launch_ks_group_rt<3, ET>(it, N, s); break;
-        case 4: launch_ks_group_rt<4, ET>(it, N, s); break;
-        case 5: launch_ks_group_rt<5, ET>(it, N, s); break;
-        case 6: launch_ks_group_rt<6, ET>(it, N, s); break;
-        case 7: launch_ks_group_rt<7, ET>(it, N, s); break;
-        case 8: launch_ks_group_rt<8, ET>(it, N, s); break;
-        default: throw gs_error("k_mfma_ks_group: row tiles outside 2..8");
-    }
-}
-template <class ET>
-void launch_ks_et(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
-                  const gsk::epilogue &epi) {
-    const ET *b = (const ET *)B;
-    ET *c = (ET *)C;
-    switch (p.dev.ks_ctw) {  // 16-column tiles per workgroup; ks_col_tiles_ct(N, CT) workgroups across N
-        case 1: launch_ks_ct<1, ET>(p, a, b, c, N, s, epi); break;
-        case 2: launch_ks_ct<2, ET>(p, a, b, c, N, s, epi); break;
-        case 4: launch_ks_ct<4, ET>(p, a, b, c, N, s, epi); break;
-        case 8: launch_ks_ct<8, ET>(p, a, b, c, N, s, epi); break;
-        default: throw gs_error("k_mfma_ks: bad column tile count");
-    }
+    const device_plan &d = it[0].p->dev;
+    for_value<2, 3, 4, 5, 6, 7, 8>(d.maxr, "k_mfma_ks_group: row tiles outside 2..8", [&](auto rt) {
+        for_value<1, 2, 3, 4>(d.seg_cap, nullptr, [&](auto maxg) {  // (MAXG 4 for any other count, as launch_ks_et)
+            launch_ks_group_k<decltype(rt)::value, decltype(maxg)::value, (int)kKsWaves, ET>(it, N, s);
+        });
+    });
 }
 }  // namespace
 
-#ifdef GS_KS_BF16_OBJECT
+#if GS_KS_OBJECT == GS_KS_BF16
 void launch_ks_bf16(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s,
                     const gsk::epilogue &epi) {
     launch_ks_et<gsk::bf16>(p, a, B, C, N, s, epi);
@@ -445,16 +373,19 @@ void launch_ks_group_bf16(const std::vector<ks_group_item> &it, uint32_t N, hipS
 uint32_t ks_group_key(const plan_state &p, uint32_t N) {
     const device_plan &d = p.dev;
     const bool w8 = d.waves == kKsWaves && d.ks_ap, w4 = d.waves == 4 && !d.ks_ap;
-    if (!p.uploaded || !d.mfma || !d.ks || d.pad_rows || N != 32 || d.lds_N != 32 || !(w8 || w4) || d.ks_persist) return 0;
+    if (!p.uploaded || !d.mfma || !d.ks || d.pad_rows || N != 32 || d.lds_N != 32 || d.ks_persist) return 0;
     if (d.weights != kWNative) return 0;  // FP8 weights: no grouped kernel is built, a batch runs single launches
-    // bf16: the grouped kernel's twins are the release instantiations (as launch_ks_k)
-    if (d.dtype == kBF16 && (d.ks_p8 || d.ks_wp || !w8)) return 0;
-    if (d.ks_wp && !w8) return 0;
-#ifndef GS_EXPERIMENTS
-    // the release build instantiates the grouped kernel for 16-byte u16-position groups on 8
-    // waves only: any other layout runs as single launches (which refuse it themselves)
-    if (d.ks_p8 || !w8) return 0;
+    if (!ks_release_layout(d)) {
+        // bf16: the grouped kernel's twins are the release instantiations (as launch_ks_k).  fp16 also groups
+        // window positions (KS_WPOS, 8 waves) and, in the experiments build, 8-bit positions and 4 waves
+        // with the overlapped layout; any other layout runs as single launches (which refuse it themselves)
+        if (d.dtype == kBF16) return 0;
+#ifdef GS_EXPERIMENTS
+        if (!(w8 || w4) || (d.ks_wp && !w8)) return 0;
+#else
+        if (!w8 || d.ks_p8) return 0;
 #endif
+    }
     // position form, dtype, NT, waves, P8, RT, MAXG: fp16 and bf16 entries, and u16 and window
     // positions, never share a launch
     return (d.ks_wp ? 1u << 21 : 0u) | (d.dtype == kBF16 ? 1u << 20 : 0u) | (d.ks_nt << 18) | (w4 ? 1u << 17 : 0u) | (d.ks_p8 ? 1u << 16 : 0u) | (d.maxr << 8) |
@@ -511,13 +442,11 @@ void debug_ks_timeline(const plan_state &p, const void *B, void *C, uint32_t N, 
     const device_arrays &a = d.replicas[0];
     const gsk::f16 *b = (const gsk::f16 *)B;
     gsk::f16 *c = (gsk::f16 *)C;
-    const bool g1 = d.seg_cap == 1;
-    switch (d.maxr) {
-        case 2: g1 ? launch_ks_k<2, 2, 1, true>(p, a, b, c, N, s, dst) : launch_ks_k<2, 2, 2, true>(p, a, b, c, N, s, dst); break;
-        case 3: g1 ? launch_ks_k<2, 3, 1, true>(p, a, b, c, N, s, dst) : launch_ks_k<2, 3, 2, true>(p, a, b, c, N, s, dst); break;
-        case 4: g1 ? launch_ks_k<2, 4, 1, true>(p, a, b, c, N, s, dst) : launch_ks_k<2, 4, 2, true>(p, a, b, c, N, s, dst); break;
-        default: g1 ? launch_ks_k<2, 5, 1, true>(p, a, b, c, N, s, dst) : launch_ks_k<2, 5, 2, true>(p, a, b, c, N, s, dst); break;
-    }
+    for_value<2, 3, 4, 5>(d.maxr, nullptr, [&](auto rt) {
+        for_value<1, 2>(d.seg_cap, nullptr, [&](auto maxg) {
+            launch_ks_k<2, decltype(rt)::value, decltype(maxg)::value, true>(p, a, b, c, N, s, dst);
+        });
+    });
     HIP_OK(hipStreamSynchronize(s));
     HIP_OK(hipMemcpy(host, dst, std::min(n, n_host) * 8, hipMemcpyDeviceToHost));
     (void)hipFree(dst);
@@ -532,6 +461,6 @@ void debug_ks_timeline(const plan_state &, const void *, void *, uint32_t, hipSt
 }
 #endif  // GS_EXPERIMENTS
 
-#endif  // !GS_KS_BF16_OBJECT
+#endif  // GS_KS_OBJECT == GS_KS_BF16
 
 }  // namespace gs

@@ -1,6 +1,7 @@
 // kernels/launch_common.hpp -- what the upload and the launch files (device_plan.hip,
-// gather_launch.hip, mfma_launch.hip, ks_launch.hip) share: the HIP error check and the
-// dynamic-LDS opt-in.
+// gather_launch.hip, mfma_launch.hip, sddmm_launch.hip and, through ks_dispatch.hpp, ks_launch.hip,
+// ks_w8_launch.hip, ks_tm_launch.hip) share: the HIP error check, the dynamic-LDS opt-in and the
+// dispatch on a plan's dtype.
 #pragma once
 
 #include "../host/gs_plan.hpp"
@@ -30,6 +31,14 @@ void grant_lds(int device, KERN kern, size_t bytes) {
                                    (int)bytes));
         g = bytes;
     }
+}
+
+// calls f with a value of the dtype's element type (float, gsk::f16 or gsk::bf16), for a launch templated on it
+template <class F>
+void by_dtype(int dtype, F &&f) {
+    if (dtype == kF32) f(float{});
+    else if (dtype == kBF16) f(__bf16{});
+    else f(_Float16{});
 }
 
 }  // namespace gs
