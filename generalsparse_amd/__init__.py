@@ -539,25 +539,97 @@ class Plan:
         return out
 
     # ------------------------------------------------------------- backward
-    def _pattern(self):
+    def _pattern(self, values=True):
         n = ctypes.c_uint64(0)
         _lib.check(self._L.gs_plan_pattern(self._h, None, None, None, 0, ctypes.byref(n)))
-        row, col, val = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64), np.zeros(n.value, np.float32)
+        row, col = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        val = np.zeros(n.value, np.float32) if values else None
         if n.value:
             _lib.check(self._L.gs_plan_pattern(self._h, row.ctypes.data_as(_lib.u64p), col.ctypes.data_as(_lib.u64p),
-                                               val.ctypes.data_as(_lib.f32p), n.value, ctypes.byref(n)))
+                                               val.ctypes.data_as(_lib.f32p) if values else None, n.value, ctypes.byref(n)))
         return row, col, val
 
     def pattern(self):
         """(row, col) of the plan's entries as uint64 arrays in the canonical order: by original row, then
         by column, stored duplicates adjacent in input order -- np.nonzero's order for a dense weight.
-        The same after any pipeline; no device is touched (gs_plan_pattern)"""
-        row, col, _ = self._pattern()
+        The same after any pipeline; no device is touched and no value is asked for, so it works while the
+        plan's host values are stale (set_values) (gs_plan_pattern)"""
+        row, col, _ = self._pattern(values=False)
         return row, col
 
     def values(self):
-        """the float32 values the plan holds, in pattern()'s order"""
+        """the float32 values the plan holds on the host, in pattern()'s order; refused (GsError) while they
+        are stale: after a set_values that changed the device only"""
         return self._pattern()[2]
+
+    # -------------------------------------------------------- value updates
+    def values_prepare(self):
+        """builds set_values' map and uploads it now (gs_plan_values_prepare): once per plan, 4 bytes per slot
+        of the layout's value array (about the bytes of the plan's A), shared by its replicas; needed before a
+        stream capture that holds the plan's first set_values"""
+        _lib.check(self._L.gs_plan_values_prepare(self._h))
+        return self
+
+    def set_values(self, values, host=False, stream=None):
+        """new values for the plan's entries, in pattern()'s order, written into the uploaded plan in place
+        (gs_plan_set_values, k_set_values): every replica then holds the bits of a fresh upload of them; the
+        plan, its arrays and every Batch / Rotation built on it stay as they are.  Enqueued on torch's current
+        stream like a launch; keeping it ordered against launches of this plan on other streams is the caller's job.
+        values: a contiguous float32 tensor of nnz elements on the plan's device -- the update then never
+        leaves the GPU, and the plan's HOST values become stale: values(), save(), fp8_layout() and the first
+        launch at another dense width refuse until a refresh; host=True also copies the tensor to the CPU and
+        refreshes them -- or a CPU tensor / numpy array: a host refresh plus the device update through a
+        temporary device copy.  Only for k_mfma_ks plans at f16 / bf16 with native weights and no CSR resident
+        (GsError otherwise, nothing launched).  Every argument is checked before the call."""
+        import torch
+        info = self.info()
+        nnz = info["nnz"]
+        if not info["replicas"]:
+            raise _refused("set_values: plan is not on the device")
+        dev = torch.device("cuda", getattr(self, "_device", 0))
+        if isinstance(values, torch.Tensor) and values.is_cuda:
+            if values.device != dev:
+                raise ValueError(f"values must be on the plan's device ({dev}), not {values.device}")
+            if values.dtype != torch.float32:
+                raise TypeError("values must be float32")
+            if not (values.dim() == 1 and values.numel() == nnz and values.is_contiguous()):
+                raise ValueError(f"values must be a contiguous vector of {nnz} elements (one per entry of pattern())")
+            d = values
+            h = values.cpu().numpy() if host else None
+        else:
+            if isinstance(values, torch.Tensor):
+                if values.dtype != torch.float32:
+                    raise TypeError("values must be float32")
+                values = values.detach().numpy()
+            h = np.asarray(values)
+            if h.dtype != np.float32:
+                raise TypeError("values must be float32")
+            if not (h.ndim == 1 and h.size == nnz):
+                raise ValueError(f"values must be a vector of {nnz} elements (one per entry of pattern())")
+            h = np.ascontiguousarray(h)
+            d = torch.from_numpy(h if h.flags.writeable else h.copy()).to(dev)  # (torch wants a writable array)
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._L.gs_plan_set_values(self._h, ctypes.c_void_p(d.data_ptr()),
+                                              h.ctypes.data_as(_lib.f32p) if h is not None else None, ctypes.c_void_p(s)))
+        if d is not values and stream is not None:
+            # (the temporary copy belongs to torch's current stream: it may not be reused before the kernel on
+            # the caller's stream has read it)
+            torch.cuda.synchronize(dev)
+        return self
+
+    def value_sources(self, dtype="f16"):
+        """(src, vals16) of the plan's k_mfma_ks layout, host only (gs_plan_value_sources): src[slot] the index
+        in pattern()'s order of the entry whose value lives in that slot of the layout's value array
+        (0xffffffff: none), vals16 the 16-bit value words exactly as upload(dtype) would lay them out under
+        the current config.  GsError for a plan set_values could not update (off k_mfma_ks, a coordinate
+        stored twice, ...)."""
+        code = _dtype_code(dtype)
+        n = ctypes.c_uint64(0)
+        _lib.check(self._L.gs_plan_value_sources(self._h, code, None, 0, ctypes.byref(n), None))
+        src, vals = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint16)
+        _lib.check(self._L.gs_plan_value_sources(self._h, code, src.ctypes.data_as(_lib.u32p), src.size, ctypes.byref(n),
+                                                 vals.ctypes.data_as(_lib.u16p)))
+        return src, vals
 
     def sddmm_prepare(self):
         """uploads the pattern for sddmm now (gs_plan_sddmm_prepare): once per plan; needed before a

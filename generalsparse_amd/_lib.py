@@ -16,6 +16,8 @@ GS_W_NATIVE = 0  # A's values in the plan's dtype
 GS_W_FP8_E4M3 = 1  # ... as OCP e4m3fn codes with one fp32 scale per row (gs_plan_upload_ex)
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
+u16p = ctypes.POINTER(ctypes.c_uint16)
+u32p = ctypes.POINTER(ctypes.c_uint32)
 u64p = ctypes.POINTER(ctypes.c_uint64)
 f32p = ctypes.POINTER(ctypes.c_float)
 f64p = ctypes.POINTER(ctypes.c_double)
@@ -38,7 +40,8 @@ class GsPlanInfo(ctypes.Structure):
                 ("n_kernels", ctypes.c_int), ("device_kernel", ctypes.c_char * 32),
                 ("index_formulas", ctypes.c_int), ("index_bytes_saved", ctypes.c_uint64),
                 ("ks_nt", ctypes.c_uint32), ("ks_head_groups", ctypes.c_uint32),
-                ("nm_tiles", ctypes.c_uint32), ("ks_wpos", ctypes.c_uint32), ("weights", ctypes.c_uint32)]
+                ("nm_tiles", ctypes.c_uint32), ("ks_wpos", ctypes.c_uint32), ("weights", ctypes.c_uint32),
+                ("host_values_stale", ctypes.c_uint32), ("value_map_bytes", ctypes.c_uint64)]
 
 
 class GsEpilogue(ctypes.Structure):
@@ -62,6 +65,9 @@ SIGNATURES = {
     "gs_linear_tile_split": ([ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
                               ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
     "gs_plan_pattern": ([ctypes.c_void_p, u64p, u64p, f32p, ctypes.c_uint64, u64p], ctypes.c_int),
+    "gs_plan_values_prepare": ([ctypes.c_void_p], ctypes.c_int),
+    "gs_plan_set_values": ([ctypes.c_void_p, ctypes.c_void_p, f32p, ctypes.c_void_p], ctypes.c_int),
+    "gs_plan_value_sources": ([ctypes.c_void_p, ctypes.c_int, u32p, ctypes.c_uint64, u64p, u16p], ctypes.c_int),
     "gs_sddmm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "gs_plan_sddmm_prepare": ([ctypes.c_void_p], ctypes.c_int),
     "gs_sddmm_geometry": ([ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),

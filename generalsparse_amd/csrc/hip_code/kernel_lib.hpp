@@ -36,6 +36,8 @@
 //   k_mfma_ks_tm     a k_mfma_ks plan on token-major activations (gs_linear: Y = X * A^T)
 //   sddmm.hpp:
 //   k_sddmm_tm       the sampled product G^T * X at a plan's pattern, token-major operands (gs_sddmm)
+//   set_values.hpp:
+//   k_set_values     an uploaded k_mfma_ks plan's values rewritten in place from a device array (gs_plan_set_values)
 //   nm_mfma.hpp:
 //   k_nm_mfma        2:4 panels on the sparse matrix cores
 //   merge_path.hpp:
@@ -54,6 +56,7 @@
 #include "mfma_ks.hpp"
 #include "mfma_ks_tm.hpp"
 #include "sddmm.hpp"
+#include "set_values.hpp"
 #include "nm_mfma.hpp"
 #include "merge_path.hpp"
 #ifdef GS_EXPERIMENTS  // opt-in kernels measured slower than the default ones

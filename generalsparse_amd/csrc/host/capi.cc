@@ -59,9 +59,18 @@ struct sddmm_state {
     int col_bytes = 0, device = 0;
 };
 
+// the value-source map of a k_mfma_ks plan (gs_plan_set_values): one per plan, shared by its replicas
+struct values_state {
+    uint32_t *src = nullptr;         // device: one u32 per slot of device_arrays::tval (gs::value_map::src)
+    uint64_t n_slots = 0;
+    std::vector<uint32_t> host_pos;  // pattern index -> position in the plan's stored nz_vals
+    int device = 0;
+};
+
 struct gs_plan {
     gs::sddmm_pattern pat;  // the pattern in canonical order, taken before any operator ran (snapshot_pattern)
     sddmm_state sd;
+    values_state vs;
     std::vector<linear_scratch> lin;  // per replica; allocated on first use, freed with the plan
     std::vector<linear_ks_state> lin_ks;  // per replica, likewise
     int lin_device = 0;
@@ -280,6 +289,14 @@ void free_sddmm(gs_plan *p) {
     p->sd = sddmm_state();
 }
 
+void free_values(gs_plan *p) {
+    if (p->vs.src) {
+        (void)hipSetDevice(p->vs.device);
+        (void)hipFree(p->vs.src);
+    }
+    p->vs = values_state();
+}
+
 // C's place behind B in that scratch: the next 256-byte boundary (the families' vector accesses)
 size_t linear_c_offset(uint64_t K, uint32_t N, size_t e) { return ((size_t)K * N * e + 255) / 256 * 256; }
 
@@ -421,6 +438,60 @@ void ensure_sddmm(gs_plan *p, hipStream_t stream, bool may_capture) {
         (void)hipSetDevice(prev);
         throw;
     }
+    GS_HIP(hipSetDevice(prev));
+}
+
+// a reader of the plan's host values (nz_vals, the pattern's val) after a device-only gs_plan_set_values
+void check_host_values(const gs_plan *p, const char *who) {
+    GS_CHECK(!p->st.host_values_stale, std::string(who) + ": the plan's host values are stale -- gs_plan_set_values changed the "
+             "values on the device only; pass the values as host_values to gs_plan_set_values (Plan.set_values(..., host=True)) first");
+}
+
+// gs_plan_set_values' plan: every refusal, before anything is built, uploaded or launched
+void check_values_plan(gs_plan *p) {
+    GS_CHECK(!divided(p), "value update: an undivided plan only (this one is divided into sub-matrices)");
+    const gs::plan_state &st = p->st;
+    GS_CHECK(st.uploaded, "value update: plan is not on the device");
+    const gs::device_plan &d = st.dev;
+    GS_CHECK(d.dtype == gs::kF16 || d.dtype == gs::kBF16, "value update: f16 and bf16 plans only (an f32 plan runs no k_mfma_ks)");
+    GS_CHECK(d.weights == gs::kWNative, "value update: a plan with FP8 weights holds codes and row scales, not values of its dtype");
+    GS_CHECK(d.mfma && d.ks && !d.pad_rows, "value update: k_mfma_ks plans without padded rows only (this plan runs " +
+                                                (d.kernel.empty() ? std::string("a gather family") : d.kernel) + ")");
+    GS_CHECK(!p->pat.rp.empty(), "value update: the plan holds no pattern (read from a plan file whose pipeline padded or "
+                                 "divided the matrix, or past 32-bit offsets)");
+    for (const gs::device_arrays &a : d.replicas)
+        GS_CHECK(!a.col && !a.val, "value update: the plan ran at another dense width and holds its CSR on the device, a second "
+                                   "copy of the values in another order; updating that copy is out of scope (upload the plan again)");
+}
+
+// the map on the plan's device: built and uploaded once per plan, by the first gs_plan_set_values or by
+// gs_plan_values_prepare, freed with the plan and by an upload.  Synchronous, as ensure_sddmm
+void ensure_values(gs_plan *p, hipStream_t stream, bool may_capture) {
+    if (p->vs.src) return;
+    if (may_capture && capturing(stream))
+        throw gs::gs_error("gs_plan_set_values: the value map is uploaded on first use: call gs_plan_values_prepare before capturing", -2);
+    check_host_values(p, "gs_plan_values_prepare");  // (only the map is needed, but one rule for every reader)
+    gs::plan_state &st = p->st;
+    gs::value_map vm = gs::build_value_map(*st.meta, st.cg->get_kernel_spec(), st.cg->get_sub_matrix_id(), st.M, st.K,
+                                           st.dev.dtype, p->pat);
+    GS_CHECK(vm.src.size() == st.dev.ks_val_slots && vm.src.size() % 8 == 0 && vm.layout_hash == st.dev.ks_hash,
+             "value update: the config changed since the upload: the map is not the uploaded layout's (upload the plan again)");
+    int prev = 0;
+    GS_HIP(hipGetDevice(&prev));
+    GS_HIP(hipSetDevice(st.dev.device));
+    uint32_t *src = nullptr;
+    try {
+        GS_HIP(hipMalloc((void **)&src, vm.src.size() * sizeof(uint32_t)));
+        GS_HIP(hipMemcpy(src, vm.src.data(), vm.src.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    } catch (...) {  // nothing half-uploaded stays behind
+        if (src) (void)hipFree(src);
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    p->vs.src = src;
+    p->vs.n_slots = vm.src.size();
+    p->vs.host_pos = std::move(vm.host_pos);
+    p->vs.device = st.dev.device;
     GS_HIP(hipSetDevice(prev));
 }
 
@@ -961,6 +1032,8 @@ int gs_plan_upload_ex(gs_plan_t *p, int dtype, int weights, const float *row_sca
         free_groups(p);
         free_linear(p);  // (the dtype or the device may have changed)
         free_sddmm(p);
+        free_values(p);  // (the layout is rebuilt from the host values: they are current again)
+        p->st.host_values_stale = false;
         for (gs::plan_state *s : ks) {
             if (s->parent_row_base < 0) continue;
             auto g = std::find_if(p->groups.begin(), p->groups.end(), [&](const parent_group &x) {
@@ -1023,6 +1096,7 @@ int gs_plan_fp8_layout(gs_plan_t *p, const float *row_scale, uint8_t *codes, uin
     return guard([&] {
         GS_CHECK(p && n_codes && (cap == 0 || codes), "null argument");
         GS_CHECK(!divided(p), "FP8 weights: an undivided plan only (this one is divided into sub-matrices)");
+        check_host_values(p, "gs_plan_fp8_layout");
         gs::plan_state &s = p->st;
         GS_CHECK(s.cg && s.cg->is_compiled(), "plan must be compiled first");
         const int sb = s.cg->get_sub_matrix_id();
@@ -1128,11 +1202,64 @@ int gs_plan_pattern(gs_plan_t *p, uint64_t *row, uint64_t *col, float *val, uint
         GS_CHECK(!pat.rp.empty(), "the plan holds no pattern (read from a plan file whose pipeline padded or divided the matrix, or past 32-bit offsets)");
         *nnz = pat.nnz();
         if (cap == 0) return;
-        GS_CHECK(cap >= pat.nnz() && row && col && val, "gs_plan_pattern: the buffers hold fewer than nnz entries");
+        GS_CHECK(cap >= pat.nnz() && row && col, "gs_plan_pattern: the buffers hold fewer than nnz entries");
+        if (val) check_host_values(p, "gs_plan_pattern");
         for (uint64_t r = 0; r < pat.rows(); r++)
             for (uint32_t e = pat.rp[r]; e < pat.rp[r + 1]; e++) row[e] = r;
         std::copy(pat.col.begin(), pat.col.end(), col);
-        std::copy(pat.val.begin(), pat.val.end(), val);
+        if (val) std::copy(pat.val.begin(), pat.val.end(), val);
+    });
+}
+
+int gs_plan_value_sources(gs_plan_t *p, int dtype, uint32_t *src, uint64_t cap, uint64_t *n_slots, uint16_t *vals16) {
+    return guard([&] {
+        GS_CHECK(p && n_slots && (cap == 0 || src), "null argument");
+        GS_CHECK(!divided(p), "value update: an undivided plan only (this one is divided into sub-matrices)");
+        gs::plan_state &s = p->st;
+        GS_CHECK(s.cg && s.cg->is_compiled(), "plan must be compiled first");
+        if (vals16 && cap) check_host_values(p, "gs_plan_value_sources");
+        const gs::value_map vm = gs::build_value_map(*s.meta, s.cg->get_kernel_spec(), s.cg->get_sub_matrix_id(), s.M, s.K, dtype, p->pat);
+        *n_slots = vm.src.size();
+        if (cap == 0) return;
+        GS_CHECK(cap >= vm.src.size(), "gs_plan_value_sources: the buffers hold fewer than n_slots entries");
+        std::copy(vm.src.begin(), vm.src.end(), src);
+        if (vals16) std::copy(vm.vals16.begin(), vm.vals16.end(), vals16);
+    });
+}
+
+int gs_plan_values_prepare(gs_plan_t *p) {
+    return guard([&] {
+        GS_CHECK(p, "null plan");
+        check_values_plan(p);
+        ensure_values(p, nullptr, false);
+    });
+}
+
+int gs_plan_set_values(gs_plan_t *p, const float *dev_values, const float *host_values, gs_stream_t stream) {
+    return guard([&] {
+        // every check before the map's upload, the launches and the host rewrite
+        GS_CHECK(p, "null plan");
+        GS_CHECK(dev_values || host_values, "gs_plan_set_values: neither device nor host values");
+        check_values_plan(p);
+        hipStream_t s = (hipStream_t)stream;
+        ensure_values(p, s, true);
+        gs::plan_state &st = p->st;
+        if (dev_values) {
+            // (stale from the first launch on: a launch that throws may have updated some replicas)
+            if (!host_values) st.host_values_stale = true;
+            for (const gs::device_arrays &a : st.dev.replicas)
+                gs::launch_set_values(st.dev.dtype, a.tval, p->vs.src, dev_values, p->vs.n_slots / 8, s);
+        }
+        if (host_values) {
+            std::vector<double> &nz = st.meta->get_element(gs::GLOBAL_META, "nz_vals", st.cg->get_sub_matrix_id())->meta_data_arr->f_mut();
+            const uint64_t nnz = p->pat.nnz();
+            GS_CHECK(nz.size() == nnz && p->vs.host_pos.size() == nnz, "gs_plan_set_values: the plan's stored values changed");
+            for (uint64_t e = 0; e < nnz; e++) {
+                nz[p->vs.host_pos[e]] = (double)host_values[e];
+                p->pat.val[e] = host_values[e];
+            }
+            st.host_values_stale = false;
+        }
     });
 }
 
@@ -1383,6 +1510,8 @@ int gs_plan_info_get(gs_plan_t *p, gs_plan_info *info) {
             info->nm_tiles = s.dev.nm ? s.dev.nm_tiles : 0;
             info->weights = (uint32_t)s.dev.weights;
         }
+        info->value_map_bytes = p->vs.src ? p->vs.n_slots * sizeof(uint32_t) : 0;
+        info->host_values_stale = p->st.host_values_stale ? 1 : 0;
     });
 }
 
@@ -1480,6 +1609,7 @@ int gs_index_compression_of_array(const uint64_t *a, uint64_t n, int type_ori, i
 int gs_plan_save(gs_plan_t *p, const char *path) {
     return guard([&] {
         GS_CHECK(p && path, "null argument");
+        check_host_values(p, "gs_plan_save");
         std::vector<const gs::plan_state *> ks;
         for (gs::plan_state *s : kernel_states(p)) ks.push_back(s);
         gs::save_plan(ks, path);
@@ -1536,6 +1666,7 @@ void gs_plan_free(gs_plan_t *p) {
         free_groups(p);
         free_linear(p);
         free_sddmm(p);
+        free_values(p);
         gs::free_device(p->st);
         for (auto &kv : p->subs) gs::free_device(*kv.second);
     } catch (...) {

@@ -446,11 +446,13 @@ bool build_mfma_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<ui
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,
                     int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype,
-                    const std::vector<uint8_t> *codes) {
+                    const std::vector<uint8_t> *codes, std::vector<uint32_t> *src) {
     const uint64_t nb = tb_rows.size() - 1;
     if (nb == 0 || K == 0) { why = "empty plan"; return false; }
     if (N == 0 || N % 8 != 0) { why = "N must be a multiple of 8"; return false; }
     GS_CHECK(!codes || codes->size() == vals.size(), "k_mfma_ks layout: one e4m3 code per value");
+    GS_CHECK(!(codes && src), "k_mfma_ks layout: value sources are those of the 16-bit values");
+    if (src) src->clear();
     // KS_WAVES = 16: twice the waves (more loads in flight per CU) when their stages fit LDS
     uint32_t W = kKsWaves;
     uint64_t rmax = 0;
@@ -607,6 +609,7 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
     std::vector<uint8_t> hpos8, hwin;
     std::vector<uint64_t> cur;
     std::vector<uint16_t> pos, hv, prow, pcol, hpos, hval;
+    std::vector<uint32_t> sidx;  // src: the step's entries as indices into vals
     for (uint64_t g = 0; g < nb; g++) {
         const uint64_t r0 = tb_rows[g], R = tb_rows[g + 1] - r0;
         cur.assign(R, 0);
@@ -618,17 +621,22 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
                 hv.clear();
                 prow.clear();
                 pcol.clear();
+                sidx.clear();
                 for (uint64_t i = 0; i < R; i++) {
                     uint64_t e = cur[i];
                     for (; e < row_ptr[r0 + i + 1] && col[e] < lim; e++) {
                         pos.push_back((uint16_t)(i * RS + (col[e] - base)));
                         prow.push_back((uint16_t)i);
                         pcol.push_back((uint16_t)(col[e] - base));
-                        // (FP8 weights: the entry's code rides through the ordering in the 16-bit slot)
-                        hv.push_back(codes ? (uint16_t)(*codes)[e] : value_bits16(vals[e], dtype));
+                        // (FP8 weights: the entry's code rides through the ordering in the 16-bit slot; value
+                        // sources: 1 + the entry's place in the step -- at most 128 rows x 32 columns -- does,
+                        // and the values follow once the slots are known)
+                        sidx.push_back((uint32_t)e);
+                        hv.push_back(src ? (uint16_t)sidx.size() : codes ? (uint16_t)(*codes)[e] : value_bits16(vals[e], dtype));
                     }
                     cur[i] = e;
                 }
+                GS_CHECK(sidx.size() < 65536u, "k_mfma_ks step holds more than 65535 entries");
                 size_t before, ng;
                 if (t.WP && t.GH && s < HS) {  // a head step: its fixed slot
                     hpos8.clear();
@@ -661,6 +669,15 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
                     ng = (t.pos.size() - before) / 8;
                 }
                 GS_CHECK(ng <= t.GCAP, "k_mfma_ks step exceeds its capacity");
+                if (src) {  // the step's slots: place in the step -> entry, and the entry's value word
+                    src->resize(t.val.size(), kNoValue);
+                    for (size_t k = before; k < before + ng * 8; k++) {
+                        if (!t.val[k]) continue;  // a zero-row pad
+                        const uint32_t e = sidx[t.val[k] - 1u];
+                        (*src)[k] = e;
+                        t.val[k] = value_bits16(vals[e], dtype);
+                    }
+                }
                 t.steps.push_back((uint32_t)(before / 8));
                 t.steps.push_back((uint32_t)ng);
             }
@@ -673,6 +690,7 @@ bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint
     else
         t.pos.insert(t.pos.end(), 8, (uint16_t)pad_h);  // spare group: loads past a wave's last step
     t.val.insert(t.val.end(), 8, 0);
+    if (src) src->resize(t.val.size(), kNoValue);
     if (codes) {  // 8 bytes per group in place of the 8 x u16 (pad slots: 0, which is code 0)
         t.val8.assign(t.val.begin(), t.val.end());
         std::vector<uint16_t>().swap(t.val);
@@ -915,7 +933,7 @@ void check_fp8_layout(const mc_layout &mc, uint64_t K) {
 }
 
 mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t K, int dtype,
-                                    const fp8_request *w8) {
+                                    const fp8_request *w8, bool want_src) {
     mc_layout L;
     const config_t cfg = get_config();
     const int64_t Nd = cfg.DENSE_MATRIX_SIZE;
@@ -983,8 +1001,12 @@ mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &s
         quantize_fp8_rows(cr.val.data(), vrow.data(), cr.val.size(), row_num, w8->row_scale, codes.data(), L.w8_scale.data());
     }
     if (cfg.MFMA_KS && build_ks_tiles(L.tbr, cr.rp, cr.col, cr.val, K, N, cfg.KS_SPLIT, cfg.KS_MIN_ROWS, cfg.MFMA_MAX_FILL,
-                                      L.ks, L.why, dtype, w8 ? &codes : nullptr)) {
+                                      L.ks, L.why, dtype, w8 ? &codes : nullptr, want_src ? &L.ks_src : nullptr)) {
         L.kind = mc_layout::KS;
+        if (want_src) {
+            L.cr_rp = cr.rp;
+            L.cr_col = cr.col;
+        }
         return L;
     }
     if (bf) {
@@ -1014,6 +1036,84 @@ mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &s
     L.rows_ksplit = (L.rows.nc + L.rows_ncs - 1) / L.rows_ncs;  // no empty split
     L.kind = mc_layout::ROWS;
     return L;
+}
+
+uint64_t ks_layout_hash(const ks_tiles &t) {
+    uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a over the arrays' words
+    auto mix = [&](uint64_t x) { h = (h ^ x) * 0x100000001b3ull; };
+    for (uint32_t x : {t.S, t.NS, t.RT, t.MAXG, t.GCAP, t.W, t.CT, t.GH, (uint32_t)t.P8, (uint32_t)t.WP}) mix(x);
+    mix(t.pos.size());
+    for (uint16_t x : t.pos) mix(x);
+    mix(t.pos8.size());
+    for (uint8_t x : t.pos8) mix(x);
+    mix(t.win.size());
+    for (uint8_t x : t.win) mix(x);
+    mix(t.steps.size());
+    for (uint32_t x : t.steps) mix(x);
+    return h;
+}
+
+value_map build_value_map(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t M, uint64_t K, int dtype,
+                          const sddmm_pattern &pat) {
+    GS_CHECK(dtype == kF16 || dtype == kBF16, "value update: f16 and bf16 plans only (an f32 plan runs no k_mfma_ks)");
+    GS_CHECK(!pat.rp.empty(), "value update: the plan holds no pattern (read from a plan file whose pipeline padded or "
+                              "divided the matrix, or past 32-bit offsets)");
+    // (trailing rows without entries leave the plan fewer rows than the matrix: that is no padding)
+    GS_CHECK(pat.rows() == M && row_num_of_sub_matrix(m, sb) <= M, "value update: a plan without padded rows only");
+    GS_CHECK(!sp.interleaved, "value update: not for interleaved storage");
+    for (uint64_t r = 0; r < M; r++)
+        for (uint32_t e = pat.rp[r] + 1; e < pat.rp[r + 1]; e++)
+            GS_CHECK(pat.col[e] != pat.col[e - 1], "value update: the pattern holds coordinate (" + std::to_string(r) + ", " +
+                                                       std::to_string(pat.col[e]) + ") twice; the layout sums such entries, "
+                                                       "which no gather of values expresses");
+    mc_layout mc = choose_matrix_core_layout(m, sp, sb, K, dtype, nullptr, true);
+    static const char *const names[] = {"a gather family", "k_mfma_rows", "k_mfma_ks", "k_nm_mfma", "k_mfma_bm"};
+    GS_CHECK(mc.kind == mc_layout::KS, std::string("value update: k_mfma_ks plans only: this plan compiles to ") + names[mc.kind] +
+                                           (mc.why.empty() ? "" : " (" + mc.why + ")"));
+    const std::vector<uint64_t> *order =
+        m.is_exist(GLOBAL_META, "original_nz_row_indices", sb) ? &m.u(GLOBAL_META, "original_nz_row_indices", sb) : nullptr;
+    // (stored row, column) -> pattern index: the row back through the plan's row order, the column by search
+    auto find = [&](uint64_t r, uint64_t c) -> uint32_t {
+        if (order) {
+            GS_CHECK(r < order->size(), "value update: a stored row without an original row");
+            r = (*order)[r];
+        }
+        GS_CHECK(r < M, "value update: a stored row outside the matrix");
+        const auto b = pat.col.begin() + pat.rp[r], e = pat.col.begin() + pat.rp[r + 1];
+        const auto it = std::lower_bound(b, e, c);
+        GS_CHECK(it != e && *it == c, "value update: the plan stores an entry its pattern does not hold (padding entries)");
+        return (uint32_t)(it - pat.col.begin());
+    };
+    const uint64_t nnz = pat.nnz();
+    value_map v;
+    // canonical entry -> pattern index, each pattern entry once
+    const uint64_t nr = mc.cr_rp.size() - 1;
+    GS_CHECK(mc.cr_col.size() == nnz, "value update: the layout holds other entries than the pattern");
+    std::vector<uint32_t> pat_of(nnz);
+    std::vector<uint8_t> seen(nnz, 0);
+    for (uint64_t r = 0; r < nr; r++)
+        for (uint32_t e = mc.cr_rp[r]; e < mc.cr_rp[r + 1]; e++) {
+            const uint32_t x = find(r, mc.cr_col[e]);
+            GS_CHECK(!seen[x], "value update: two layout entries of one pattern entry");
+            seen[x] = 1;
+            pat_of[e] = x;
+        }
+    v.src = std::move(mc.ks_src);
+    GS_CHECK(v.src.size() == mc.ks.val.size(), "value update: the map does not cover the value array");
+    for (uint32_t &s : v.src)
+        if (s != kNoValue) s = pat_of[s];
+    v.layout_hash = ks_layout_hash(mc.ks);
+    v.vals16 = std::move(mc.ks.val);
+    // pattern index -> position in the stored nz_vals
+    const auto &rows = m.u(GLOBAL_META, "nz_row_indices", sb), &col = m.u(GLOBAL_META, "nz_col_indices", sb);
+    GS_CHECK(rows.size() == nnz && col.size() == nnz, "value update: the plan stores other entries than its pattern (padding entries)");
+    v.host_pos.assign(nnz, kNoValue);
+    for (uint64_t i = 0; i < nnz; i++) {
+        const uint32_t x = find(rows[i], col[i]);
+        GS_CHECK(v.host_pos[x] == kNoValue, "value update: two stored entries of one pattern entry");
+        v.host_pos[x] = (uint32_t)i;
+    }
+    return v;
 }
 
 }  // namespace gs

@@ -6,6 +6,7 @@
 
 #include "gs_core.hpp"
 #include "code_generator.hpp"
+#include "sddmm_layout.hpp"
 #include "../hip_code/kernel_consts.hpp"
 
 #include <algorithm>
@@ -149,7 +150,11 @@ inline std::vector<uint32_t> ks_tm_tile_split(uint32_t n_tokens, uint32_t cap) {
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,
                     int64_t s_cfg, int64_t min_rows, int64_t max_fill, ks_tiles &t, std::string &why, int dtype = kF16,
-                    const std::vector<uint8_t> *codes = nullptr);  // codes: vals' e4m3 codes -> t.val8, t.val left empty
+                    const std::vector<uint8_t> *codes = nullptr,  // codes: vals' e4m3 codes -> t.val8, t.val left empty
+                    std::vector<uint32_t> *src = nullptr);  // src: per slot of t.val the index into vals of its entry (kNoValue: none)
+
+// a slot of ks_tiles::val that holds no entry: a group's zero-row padding, a head slot's spare groups, the spare group
+constexpr uint32_t kNoValue = 0xffffffffu;
 
 // k_mfma_bm upload layout: unit u = (BMTB g, K range q) of NS 32-column k-steps; per
 // (u*NS + step)*64 + lane one 8-byte record (rec[2i] = mask bytes of tiles 0..3, rec[2i+1]
@@ -204,12 +209,37 @@ struct mc_layout {
     bool nm_nt = false;                    // k_nm_mfma: A's panel blocks by non-temporal loads (NM_NT)
     uint32_t nm_split = 1, nm_ncs = 0;     // ... K ranges per row block, 256-column chunks per range
     std::vector<float> w8_scale;  // FP8 weights (KS): the scale of every row of the plan
+    // value sources (KS, asked for by choose_matrix_core_layout's want_src): per slot of ks.val the canonical
+    // entry it holds (kNoValue: none), and the canonical rows themselves (the plan's stored row order)
+    std::vector<uint32_t> ks_src, cr_rp;
+    std::vector<uint64_t> cr_col;
     std::string why;  // why NONE
 };
 // w8 (null: the dtype's own values): a k_mfma_ks layout gets ks.val8 and w8_scale instead of ks.val; the
 // caller checks the layout with check_fp8_layout
 mc_layout choose_matrix_core_layout(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t K, int dtype,
-                                    const fp8_request *w8 = nullptr);
+                                    const fp8_request *w8 = nullptr, bool want_src = false);
+
+// The value-source map of a compiled k_mfma_ks plan (gs_plan_set_values, k_set_values): where every slot of
+// the layout's value array -- ks_tiles::val, on the device device_arrays::tval -- takes its value from.
+//   src[slot]     index in the plan's pattern (canonical order) of the entry the slot holds, kNoValue for a
+//                 slot without one.  The layouts that pad a group with copies of one of its entries (KS_WPOS,
+//                 KS_POS8) name that entry in the copies too: both slots scatter to one place
+//   host_pos[e]   position of pattern entry e in the plan's stored nz_vals
+//   vals16        the value words exactly as the upload lays them out at `dtype` under the current config
+// Built from the same choose_matrix_core_layout call as the upload's, so it is the map of that layout.
+// Throws a gs_error: a plan off k_mfma_ks, with padded rows or padding entries, interleaved storage, or a
+// pattern that holds a coordinate twice (canonical_rows sums those: no gather expresses that)
+struct value_map {
+    std::vector<uint32_t> src, host_pos;
+    std::vector<uint16_t> vals16;
+    uint64_t layout_hash = 0;  // ks_layout_hash of the layout the map belongs to
+};
+// a hash of everything that places a k_mfma_ks layout's values (positions, windows, step records, geometry): the
+// upload keeps it, so a map built later -- under a config that may have changed -- is known to be that layout's
+uint64_t ks_layout_hash(const ks_tiles &t);
+value_map build_value_map(const meta_data_set &m, const kernel_spec &sp, int sb, uint64_t M, uint64_t K, int dtype,
+                          const sddmm_pattern &pat);
 // FP8 weights run on k_mfma_ks in the release layout only (CT = 2: a plan built for 17 .. 32 columns, 8
 // waves, the apart layout, 16-bit positions, the static grid, ks_tm_fits, K % 8 == 0): throws a gs_error
 // that names the condition a layout misses

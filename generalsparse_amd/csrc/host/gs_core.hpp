@@ -164,6 +164,7 @@ class universal_array {
     const std::vector<uint64_t> &u() const { return u_; }
     const std::vector<double> &f() const { return f_; }
     std::vector<uint64_t> &u_mut() { return u_; }
+    std::vector<double> &f_mut() { return f_; }
     // code_source_data.cc:383-413: smallest unsigned type that holds the max
     data_type get_compress_data_type() const;
     uint64_t max_integer() const;

@@ -77,6 +77,8 @@ struct device_plan {
                         // (t0 BMTB rows, tcol/tval groups; ks_ns k-steps per range,
                         // RT in maxr, MAXG in seg_cap, ws slabs + t2 arrivals when ksplit > 1)
     uint32_t ks_ns = 0, ks_gcap = 0;
+    uint64_t ks_val_slots = 0;  // k_mfma_ks: 16-bit words of tval (ks_tiles::val: 8 per entry group, the spare group too)
+    uint64_t ks_hash = 0;       // ... and ks_layout_hash of the uploaded layout (gs_plan_set_values' map must be its map)
     bool bmkb = false;  // ... k_mfma_kb: k_mfma_ks pipeline on the bitmap layout (8 waves)
     bool bm2 = false;   // ... k_mfma_bm2: one wave per row tile (W = RT), B slice of ks_ns k-steps in LDS
     bool bm = false;    // k_mfma_bm: bitmap records (tcol), step bases (t1), values (tval), t0 BMTB rows;
@@ -117,6 +119,10 @@ struct plan_state {
     uint64_t M = 0, K = 0, nnz = 0;
     device_plan dev;
     bool uploaded = false;
+    // gs_plan_set_values changed the values on the device only: the host copies (nz_vals, the pattern's val) are
+    // the old ones until a host refresh or an upload; every reader of them refuses meanwhile (ensure_csr,
+    // gs_plan_save, gs_plan_fp8_layout, gs_plan_pattern with values)
+    bool host_values_stale = false;
     // a sub-matrix of row_nz_matrix_div_operator: its row indices refer to the divided
     // sub-matrix (rows [parent_row_base, parent_row_base + parent_rows) of C); -1 otherwise
     int64_t parent_row_base = -1;
@@ -216,6 +222,9 @@ void launch_ks_group(const std::vector<ks_group_item> &it, uint32_t N, hipStream
 // (sddmm_layout.hpp); G: n x M, X: n x K of dtype (kF16 / kBF16), out: fp32.  Allocates nothing
 void launch_sddmm(int dtype, int col_bytes, const void *G, const void *X, const uint32_t *rp, const void *cols, float *out,
                   uint32_t n, uint64_t M, uint64_t K, hipStream_t s);
+// set_values_launch.hip: k_set_values (gs_plan_set_values).  tval: n_groups x 8 words of dtype (kF16 / kBF16) rewritten
+// from values[src[slot]] (src: n_groups x 8 u32 on the device, kNoValue: the slot becomes 0).  Allocates nothing
+void launch_set_values(int dtype, void *tval, const uint32_t *src, const float *values, uint64_t n_groups, hipStream_t s);
 void launch_bm(const plan_state &p, const device_arrays &a, const void *B, void *C, uint32_t N, hipStream_t s);
 void debug_bm_timeline(const plan_state &p, const void *B, void *C, uint32_t N, hipStream_t s, uint64_t *host,
                        size_t n_host);

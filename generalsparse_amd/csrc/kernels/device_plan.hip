@@ -285,6 +285,8 @@ void upload_ks(upload_ctx &u) {
     if (kt.WP) a.tw = dev_copy(d, kt.win);
     // FP8 weights: 8 bytes per group (e4m3 codes) in place of the 8 x u16
     a.tval = d.weights == kWFp8 ? (void *)dev_copy(d, kt.val8) : (void *)dev_copy(d, kt.val);
+    d.ks_val_slots = kt.val.size();
+    d.ks_hash = ks_layout_hash(kt);
     a.t1 = dev_copy(d, kt.steps);
     d.bytes_tile = d.bytes_A - before;
     // ... and the rows' scales (M fp32, indexed as the epilogue's bias is): bytes of A, not of its tiles
@@ -744,6 +746,10 @@ void ensure_csr(plan_state &p) {
     bool need = false;
     for (device_arrays &a : p.dev.replicas) need |= !a.col;
     if (!need) return;
+    // (the CSR would be built from the values of before the update: a stale launch through the gather fallback)
+    GS_CHECK(!p.host_values_stale, "this launch needs the plan's CSR, which is built from its host values, and those are stale -- "
+                                   "gs_plan_set_values changed the values on the device only; pass the values as host_values "
+                                   "to gs_plan_set_values (Plan.set_values(..., host=True)) first");
     int prev = 0;
     HIP_OK(hipGetDevice(&prev));
     for (device_arrays &a : p.dev.replicas)

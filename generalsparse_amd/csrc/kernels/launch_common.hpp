@@ -1,5 +1,5 @@
 // kernels/launch_common.hpp -- what the upload and the launch files (device_plan.hip,
-// gather_launch.hip, mfma_launch.hip, sddmm_launch.hip and, through ks_dispatch.hpp, ks_launch.hip,
+// gather_launch.hip, mfma_launch.hip, sddmm_launch.hip, set_values_launch.hip and, through ks_dispatch.hpp, ks_launch.hip,
 // ks_w8_launch.hip, ks_tm_launch.hip) share: the HIP error check, the dynamic-LDS opt-in and the
 // dispatch on a plan's dtype.
 #pragma once

@@ -11,11 +11,17 @@ Inference only by default.  Gradients are opt-in:
 
 The backward pass is the engine's own: grad_x = Plan.linear of the transposed weight (a second plan, so
 the weight is resident twice), grad_values = Plan.sddmm (k_sddmm_tm, the product sampled at the
-weight's non-zeros, in float32).  Once differentiable; FP8-weight layers stay inference only."""
+weight's non-zeros, in float32).  Once differentiable; FP8-weight layers stay inference only.
+
+sync_values() carries layer.values into the uploaded plans on the GPU (Plan.set_values, k_set_values): no
+plan is rebuilt, the plan objects and their device arrays stay where they are.  By default it also copies
+the values to the CPU and refreshes the plans' host copies; sync_values(host=False) leaves the GPU not at
+all, at the price of stale host values (Plan.values(), Plan.save() and a launch at another width refuse
+until a sync_values() with host=True).  sync_values(rebuild=True) is the host-side rebuild of both plans."""
 import numpy as np
 import torch
 
-from . import GS_W_FP8_E4M3, Plan, _check_activation, _dtype_code, _torch_dtype, _weights_code
+from . import GS_W_FP8_E4M3, GsError, Plan, _check_activation, _dtype_code, _torch_dtype, _weights_code
 
 GRAD_MODES = (None, "input", "all")
 
@@ -77,8 +83,10 @@ class SparseLinear(torch.nn.Module):
     bits (ReLU with a residual runs it a second time, without the residual, for the mask).  The
     backward needs plan_T, a plan of the transposed weight built from the pattern with the layer's
     pipeline, token width, dtype and device -- on the first backward, or by prepare_backward() -- which
-    DOUBLES the resident weight.  The forward keeps running on the values the plan was built from:
-    after an optimizer step sync_values() rebuilds both plans from layer.values (host side, slow).
+    DOUBLES the resident weight.  The forward keeps running on the values the plans hold: after an
+    optimizer step sync_values() writes layer.values into both uploaded plans in place, on the GPU (one
+    small kernel per plan; the plans' gather maps, 4 bytes per value slot each, are uploaded by
+    prepare_backward or by the first sync_values).
     A layer with FP8 weights is inference only: asking it for grad raises."""
 
     def __init__(self, plan, bias=None, activation=None, grad=None):
@@ -87,6 +95,7 @@ class SparseLinear(torch.nn.Module):
         _check_grad(grad)
         self.plan, self.activation, self.grad = plan, activation, grad
         self.plan_T = None
+        self._order = None  # plan_T's entries in layer.values' order: an index tensor on the device (prepare_backward)
         info = plan.info()
         if grad is not None and info["weights"] == GS_W_FP8_E4M3:
             raise ValueError("a SparseLinear with FP8 weights is inference only: the transposed product would run on "
@@ -155,7 +164,9 @@ class SparseLinear(torch.nn.Module):
 
     def prepare_backward(self):
         """builds plan_T, the plan of the transposed weight that grad_x runs on, now rather than in the
-        first backward (host-side plan building and an upload; the weight is then resident twice)"""
+        first backward (host-side plan building and an upload; the weight is then resident twice).  With
+        grad="all" it also uploads both plans' value maps (Plan.values_prepare), so that a later
+        sync_values() allocates nothing"""
         if self.grad is None:
             raise RuntimeError("SparseLinear(grad=None) is inference only: build it with grad='input' or 'all'")
         if self.plan_T is None:
@@ -163,21 +174,66 @@ class SparseLinear(torch.nn.Module):
             val = self._current_values()
             order = np.lexsort((row, col))  # by column, then row: the transposed weight, row-major
             self.plan_T = self._plan_of(self.in_features, self.out_features, col[order], row[order], val[order])
+            self._order = None
+            if self.grad == "all":
+                self._order = torch.from_numpy(order.astype(np.int64)).to(self.values.device)
+        if self.grad == "all":
+            for plan in (self.plan, self.plan_T):
+                try:
+                    plan.values_prepare()
+                except GsError:
+                    pass  # (a plan set_values refuses: sync_values rebuilds it on the host)
         return self
 
-    def sync_values(self):
-        """rebuilds the plan (and plan_T, if built) from the pattern and the current layer.values, so that
-        an optimizer step reaches the forward.  The slow, host-side way: two plan builds and uploads.  For
-        from_dense layers with grad="all", which remember how their plan was built."""
-        if self.grad != "all" or not self._build["rebuild"]:
-            raise RuntimeError("sync_values is for SparseLinear.from_dense(..., grad='all') layers")
+    def _rebuild(self, transposed):
+        """the host-side way: one plan built from the pattern and the current layer.values, and uploaded"""
+        if not self._build["rebuild"]:
+            raise RuntimeError("rebuilding a plan on the host is for SparseLinear.from_dense layers, which remember how "
+                               "their plan was built")
+        if transposed:
+            self.plan_T = None
+            return self.prepare_backward()
         row, col = self.plan.pattern()
-        val = np.ascontiguousarray(self._current_values())
-        had_T = self.plan_T is not None
-        self.plan = self._plan_of(self.out_features, self.in_features, row, col, val)
-        self.plan_T = None
-        if had_T:
-            self.prepare_backward()
+        self.plan = self._plan_of(self.out_features, self.in_features, row, col, np.ascontiguousarray(self._current_values()))
+        return self
+
+    def sync_values(self, rebuild=False, host=True):
+        """carries the current layer.values into the plan (and plan_T, if built), so that an optimizer step
+        reaches the forward and the backward.  On the GPU: Plan.set_values rewrites the uploaded plans' value
+        arrays in place (k_set_values); no plan is rebuilt, layer.plan and layer.plan_T stay the same objects
+        with the same device arrays, for any layer with grad="all", from_dense or wrapped around an uploaded plan.
+        host=True (the default) also copies the values to the CPU and refreshes the plans' host copies, so
+        Plan.values(), Plan.save() and a launch at another dense width keep working; host=False leaves the
+        GPU not at all and leaves those host copies stale (they refuse until a sync_values() with host=True).
+        A plan set_values refuses -- one off k_mfma_ks, or one that holds its CSR on the device, as plan_T does
+        once it ran the three-launch path (out_features not a multiple of 8) -- is rebuilt on the host instead,
+        that plan only.  rebuild=True is the host-side way for both: two plan builds and uploads (slow; for
+        from_dense layers, which remember how their plan was built)."""
+        if self.grad != "all":
+            raise RuntimeError("sync_values is for SparseLinear layers with grad='all'")
+        if rebuild:
+            had_T = self.plan_T is not None
+            self._rebuild(False)
+            self.plan_T = None
+            if had_T:
+                self.prepare_backward()
+            return self
+        values = self.values.detach()
+        if not values.is_contiguous():
+            values = values.contiguous()
+        try:
+            self.plan.set_values(values, host=host)
+        except GsError as e:
+            if e.code != -1:  # (only a refusal, which launched nothing, falls back)
+                raise
+            self._rebuild(False)
+        if self.plan_T is not None:
+            try:
+                self.plan_T.set_values(values[self._order], host=host)
+            except GsError as e:
+                if e.code != -1:
+                    raise
+                self._rebuild(True)
         return self
 
     def forward(self, x, residual=None):

@@ -75,6 +75,8 @@ typedef struct {
     uint32_t nm_tiles;            /* k_nm_mfma: 16-row tiles per workgroup (NM_TILES / the upload's rule) */
     uint32_t ks_wpos;             /* k_mfma_ks: one-byte window positions (KS_WPOS; 0: the u16 layout) */
     uint32_t weights;             /* GS_W_NATIVE / GS_W_FP8_E4M3, as uploaded (tile_bytes / device_bytes_A: the true bytes) */
+    uint32_t host_values_stale;   /* 1 after a device-only gs_plan_set_values, 0 after a host refresh or an upload */
+    uint64_t value_map_bytes;     /* device bytes of gs_plan_set_values' map (once per plan); 0 until prepared */
 } gs_plan_info;
 
 const char *gs_last_error(void);
@@ -227,8 +229,45 @@ int gs_linear_tile_split(uint64_t row_blocks, int k_ranges, int row_tiles, int n
  * holds of every entry; *nnz their number.  cap == 0 only returns *nnz; a smaller cap than nnz is
  * refused.  The pattern is taken when the plan is created, so it is the same after any pipeline (a
  * sorted plan's row order, interleaved storage and padding entries never reach it) and needs no upload.
- * A plan read by gs_plan_load has it unless its pipeline padded or divided the matrix (GS_ERR). */
+ * A plan read by gs_plan_load has it unless its pipeline padded or divided the matrix (GS_ERR).
+ * val may be NULL: only row / col are filled (and the call stays legal while the host values are stale, below). */
 int gs_plan_pattern(gs_plan_t *p, uint64_t *row, uint64_t *col, float *val, uint64_t cap, uint64_t *nnz);
+/* Value update of an uploaded plan ON THE DEVICE: only the 16-bit value words of a k_mfma_ks layout change
+ * when the weight's values do; the pattern, the k-step records and the entry positions stay.  A fixed
+ * gather map -- one u32 per slot of the layout's value array: the index in gs_plan_pattern's order of the
+ * entry the slot holds, 0xffffffff for a slot without one -- is built on the host once, and one kernel,
+ * k_set_values, rewrites the array in place from a device array of new fp32 values: per entry group 32 B of
+ * map and up to 32 B of values read, 16 B written in one store; converted as gs_convert_values does, bit for
+ * bit (so the plan then holds the bits of a fresh upload of those values).
+ * gs_plan_values_prepare: builds the map and uploads it to the plan's device (4 B per slot, about the
+ *   bytes of the plan's A itself; one map per plan, shared by its replicas, freed with the plan and by
+ *   gs_plan_upload).  Synchronous, refused inside stream capture; a second call does nothing.
+ * gs_plan_set_values: dev_values (a device pointer to nnz fp32 values in gs_plan_pattern's order, or NULL)
+ *   enqueues one k_set_values per replica on `stream`, ordered there like any launch; keeping it ordered
+ *   against launches of the same plan on OTHER streams is the caller's job.  The first call prepares the map
+ *   (so it is refused inside a capture unless gs_plan_values_prepare ran); later calls allocate nothing.
+ *   host_values (a host pointer to nnz fp32 values, or NULL) rewrites the plan's host copies, its stored
+ *   values and the pattern's: gs_plan_pattern, gs_plan_save, a later gs_plan_upload and the deferred CSR then
+ *   see them.  Given alone it is the deferred host refresh of earlier device-only updates: the caller vouches
+ *   that these are the values the device holds.  Both NULL: GS_ERR.
+ * Refused (GS_ERR, the reason in gs_last_error; nothing launched, the plan unchanged) unless the plan is on
+ * the device, undivided, on k_mfma_ks without padded rows, at GS_F16 or GS_BF16 with GS_W_NATIVE weights,
+ * holds a pattern without a coordinate stored twice (the layout sums such entries: no gather expresses
+ * that), and has no CSR resident: a plan that ran at another dense width uploaded its deferred CSR, a second
+ * copy of the values in another order, and updating that copy is out of scope (upload the plan again).
+ * Stale host values: after an update with host_values == NULL the host copies are the old ones
+ * (gs_plan_info.host_values_stale = 1) until a call with host_values or a gs_plan_upload (which uses the
+ * host values and so brings the OLD ones back).  Meanwhile every reader of them refuses with a message that
+ * names the cure: the first launch at another dense width or on gs_linear's three-launch path at another
+ * token count (the deferred CSR), gs_plan_save, gs_plan_fp8_layout, gs_plan_pattern with val.
+ * gs_plan_add_replica copies device arrays and stays legal.
+ * gs_plan_value_sources: host only, no device: the map in src and, when vals16 is not NULL, the 16-bit value
+ *   words exactly as gs_plan_upload(dtype) would lay them out under the current config (the analogue of
+ *   gs_plan_fp8_layout).  *n_slots receives their number; cap == 0 only counts.  In the layouts that pad a
+ *   group with copies of one of its entries (KS_WPOS, KS_POS8) the copies name that entry too. */
+int gs_plan_values_prepare(gs_plan_t *p);
+int gs_plan_set_values(gs_plan_t *p, const float *dev_values, const float *host_values, gs_stream_t stream);
+int gs_plan_value_sources(gs_plan_t *p, int dtype, uint32_t *src, uint64_t cap, uint64_t *n_slots, uint16_t *vals16);
 /* The sampled product on token-major operands (the weight gradient of gs_linear):
  *   out[e] = sum over t < n_tokens of G[t][row_e] * X[t][col_e],  e = 0 .. nnz - 1 in gs_plan_pattern's order.
  * G: n_tokens x M and X: n_tokens x K, row-major, one row per token, exactly as gs_linear gives Y and
