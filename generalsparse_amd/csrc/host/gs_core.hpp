@@ -137,6 +137,7 @@ struct config_t {
     int64_t MP_COL_PARTS = 0;    // merge path with MP_COL_PERM, fp32: column partitions, one pass each (0/1: off)
     int64_t LDS_DMA = 1;         // k_lds_rows at fp32 N = 32: chunks by LDS-DMA into two buffers (k_lds_rows_dma)
     int64_t LDS_KSPLIT = 0;      // k_lds_rows: workgroups per BMTB, each over a K range (fp32 slab combine; 0 auto)
+    int64_t LDS_STAGE_ANY = 0;   // k_lds_rows also for BMTBs of under 16 rows or one-row BMWs (off: the gather kernel there)
     int64_t NM_TILES = 0;        // k_nm_mfma: 16-row tiles per workgroup (0: nm_tiles_for; 2, 4, 7, 8)
     int64_t NM_KROT = 1;         // k_nm_mfma: each workgroup walks K from its own 256-row B chunk (C3 -3%,
                                  // profiles/r05ad_krot.txt; 0: every workgroup from chunk 0)

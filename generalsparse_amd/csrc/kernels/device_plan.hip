@@ -494,7 +494,8 @@ void upload_warp_total(upload_ctx &u) {
         return;
     }
     // LDS-stationary B pays off for row blocks of >= 16 rows in BMWs of >= 2 rows
-    // (C2: 20x2 31 us vs 40 us gathered; 4x1 62 us): otherwise the gather kernel
+    // (C2: 20x2 31 us vs 40 us gathered; 4x1 62 us): otherwise the gather kernel.  LDS_STAGE_ANY lifts
+    // that rule (off by default): the only way to the one-row-BMW forms of k_lds_rows (MAXR = 1)
     bool lds_worth = false;
     if (sp.tblock_parent) {
         const auto &tr = m.u(TBLOCK_META, "first_row_indices", sb);
@@ -502,7 +503,7 @@ void upload_warp_total(upload_ctx &u) {
         uint64_t mt = 0, mw = 0;
         for (size_t i = 0; i + 1 < tr.size(); i++) mt = std::max<uint64_t>(mt, tr[i + 1] - tr[i]);
         for (size_t i = 0; i + 1 < wr.size(); i++) mw = std::max<uint64_t>(mw, wr[i + 1] - wr[i]);
-        lds_worth = mt >= 16 && mw >= 2;
+        lds_worth = (mt >= 16 && mw >= 2) || get_config().LDS_STAGE_ANY != 0;
     }
     if (sp.tblock_parent && get_config().LDS_STAGE_B && lds_worth && u.dtype != kBF16) upload_lds_tiles(u, rp);
     upload_groups(!d.lds);

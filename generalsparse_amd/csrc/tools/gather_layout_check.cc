@@ -3,8 +3,10 @@
 // Python.  Built against the ASan/UBSan host objects by `make san_check` (Makefile), so the layout
 // code runs instrumented; `make build/gather_layout_check` links the plain objects.
 // Every output array is also hashed (FNV-1a-64) and compared with kExpect: the values the code
-// printed when it had just been moved, unedited, out of kernels/device_plan.hip.  `--print` prints
-// the hashes as an initializer instead of comparing them.
+// printed when it had just been moved, unedited, out of kernels/device_plan.hip, except tcol of the
+// LDS cases and src of their fp32 ones, printed again when a row's padding became copies of the row's
+// last column of the chunk (the invariants below held).  `--print` prints the hashes as an
+// initializer instead of comparing them; do that only when every invariant passes.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -20,48 +22,48 @@ static const uint64_t kExpect[] = {
     0x6c2fb0e69354de86ull,  // fp16 N=32 20x2 scalars
     0xdaa04f15cca56916ull,  // fp16 N=32 20x2 seg_start
     0xd2304bf5d1073431ull,  // fp16 N=32 20x2 seg_row_off
-    0x809d62e8f108d955ull,  // fp16 N=32 20x2 tcol
+    0x95a3dd3daf2c783aull,  // fp16 N=32 20x2 tcol
     0xc0c05cec53050638ull,  // fp16 N=32 20x2 src
     0x33648a8904d2b95eull,  // fp32 N=32 pair_banks 20x2 scalars
     0xed852e7d3e96cdd3ull,  // fp32 N=32 pair_banks 20x2 seg_start
     0xf8aa0665022883f5ull,  // fp32 N=32 pair_banks 20x2 seg_row_off
-    0xd89dea5dea0f1f4bull,  // fp32 N=32 pair_banks 20x2 tcol
-    0x03ea498a656157d9ull,  // fp32 N=32 pair_banks 20x2 src
+    0x395711456277b894ull,  // fp32 N=32 pair_banks 20x2 tcol
+    0x883aa8ecf9aabee5ull,  // fp32 N=32 pair_banks 20x2 src
     0x4cdcfdca926a18b0ull,  // fp32 N=32 pair_banks 16x4 scalars
     0x28170f11f6504e52ull,  // fp32 N=32 pair_banks 16x4 seg_start
     0x0e56c4dfc28f1315ull,  // fp32 N=32 pair_banks 16x4 seg_row_off
-    0x8b537cc978fb57eaull,  // fp32 N=32 pair_banks 16x4 tcol
-    0x8192565e53cbc1ddull,  // fp32 N=32 pair_banks 16x4 src
+    0xd86757127db70c5full,  // fp32 N=32 pair_banks 16x4 tcol
+    0x5d317ad6cd9bb50dull,  // fp32 N=32 pair_banks 16x4 src
     0x3c7740e7b62bc870ull,  // fp32 N=32 dma 20x4 scalars
     0xa56fe196e43f0475ull,  // fp32 N=32 dma 20x4 seg_start
     0x63a27f4b8f2f621dull,  // fp32 N=32 dma 20x4 seg_row_off
-    0x770140b0b1fd59c6ull,  // fp32 N=32 dma 20x4 tcol
-    0x1434ac7e0cbe3a95ull,  // fp32 N=32 dma 20x4 src
+    0x540d9f93dd795425ull,  // fp32 N=32 dma 20x4 tcol
+    0x4aba1fc8b5cb9fd1ull,  // fp32 N=32 dma 20x4 src
     0x5ecd8e2a1bbe70b3ull,  // fp32 N=32 rowslot 20x5 scalars
     0xd3ca24b00cd7e137ull,  // fp32 N=32 rowslot 20x5 seg_start
     0xbbf8167af7bb34e1ull,  // fp32 N=32 rowslot 20x5 seg_row_off
-    0xb9c2b76be6501497ull,  // fp32 N=32 rowslot 20x5 tcol
-    0xb9c6ae130df3a8f5ull,  // fp32 N=32 rowslot 20x5 src
+    0x9695c94c957d2db9ull,  // fp32 N=32 rowslot 20x5 tcol
+    0x474359b18c892bf5ull,  // fp32 N=32 rowslot 20x5 src
     0xed32955309ae8cfcull,  // fp32 N=32 rowslot 24x6 scalars
     0x8b02dcf1d844cb60ull,  // fp32 N=32 rowslot 24x6 seg_start
     0xcd52ba2c22d5aa21ull,  // fp32 N=32 rowslot 24x6 seg_row_off
-    0xfe424542b5a2ec73ull,  // fp32 N=32 rowslot 24x6 tcol
-    0x63dce0d22b201a29ull,  // fp32 N=32 rowslot 24x6 src
+    0x03577aabfcc0a3a6ull,  // fp32 N=32 rowslot 24x6 tcol
+    0x8ed9c923c44bd921ull,  // fp32 N=32 rowslot 24x6 src
     0xdd907d9c06931951ull,  // fp32 N=32 rowslot 32x8 scalars
     0x9bd89bc5b1b160c9ull,  // fp32 N=32 rowslot 32x8 seg_start
     0xac58413948778285ull,  // fp32 N=32 rowslot 32x8 seg_row_off
-    0xc089ceef64984f62ull,  // fp32 N=32 rowslot 32x8 tcol
-    0xab595e05984255c4ull,  // fp32 N=32 rowslot 32x8 src
+    0x32b063bf7df3c986ull,  // fp32 N=32 rowslot 32x8 tcol
+    0x0f444a242a0da994ull,  // fp32 N=32 rowslot 32x8 src
     0xecbf805e1c9758e6ull,  // fp32 N=32 want=3 scalars
     0x5330298ecc181bd6ull,  // fp32 N=32 want=3 seg_start
     0x473da6e16b06c155ull,  // fp32 N=32 want=3 seg_row_off
-    0x2645cc44a0c95273ull,  // fp32 N=32 want=3 tcol
-    0x0ae60af369cadb28ull,  // fp32 N=32 want=3 src
+    0x38c73947fdfbca29ull,  // fp32 N=32 want=3 tcol
+    0x46a5b4cdd7968008ull,  // fp32 N=32 want=3 src
     0x1fa9cc26d8801edaull,  // fp32 N=32 rowslot want=3 scalars
     0xe2b720f147518f4full,  // fp32 N=32 rowslot want=3 seg_start
     0xc37c98cd23588265ull,  // fp32 N=32 rowslot want=3 seg_row_off
-    0xe771d98accb91477ull,  // fp32 N=32 rowslot want=3 tcol
-    0x1a1900937263f715ull,  // fp32 N=32 rowslot want=3 src
+    0x59c20b9abdf2ed8bull,  // fp32 N=32 rowslot want=3 tcol
+    0xdcd0cfe64f88bafdull,  // fp32 N=32 rowslot want=3 src
     0xf85ee3923ea3c245ull,  // column_order hot=0 perm
     0x024bd0e37d1f2ec5ull,  // column_order hot=0 rank
     0x24edec81a2df85f5ull,  // column_order hot=17 perm
@@ -105,6 +107,81 @@ static const uint64_t kExpect[] = {
     0x7cc79a10c6209da1ull,  // bitmap rows row masks
     0xb27e99aba141bc36ull,  // bitmap rows, sub-matrix finalize rows
     0xe8b15acf9791e3adull,  // bitmap rows, sub-matrix row masks
+    0x783059749349a729ull,  // edge fp16 N=8 20x2 want=1 scalars
+    0xfc82fec943079b84ull,  // edge fp16 N=8 20x2 want=1 seg_start
+    0xfa301640a1313de9ull,  // edge fp16 N=8 20x2 want=1 seg_row_off
+    0x9d39a525be61c6ccull,  // edge fp16 N=8 20x2 want=1 tcol
+    0xf3e2c60f026f2e79ull,  // edge fp16 N=8 20x2 want=1 src
+    0x783059749349a729ull,  // edge fp16 N=8 20x2 want=2 scalars
+    0xfc82fec943079b84ull,  // edge fp16 N=8 20x2 want=2 seg_start
+    0xfa301640a1313de9ull,  // edge fp16 N=8 20x2 want=2 seg_row_off
+    0x9d39a525be61c6ccull,  // edge fp16 N=8 20x2 want=2 tcol
+    0xf3e2c60f026f2e79ull,  // edge fp16 N=8 20x2 want=2 src
+    0x7a703c8b160e685bull,  // edge fp16 N=8 20x2 want=auto scalars
+    0x0a5d4b599198d33dull,  // edge fp16 N=8 20x2 want=auto seg_start
+    0xa274f047b9bd7ebdull,  // edge fp16 N=8 20x2 want=auto seg_row_off
+    0x6c80b6fcf34e4089ull,  // edge fp16 N=8 20x2 want=auto tcol
+    0x77222d9865adec29ull,  // edge fp16 N=8 20x2 want=auto src
+    0x071d3dbd65fd335eull,  // edge fp32 N=32 pair_banks 20x2 want=1 scalars
+    0xfc82fec943079b84ull,  // edge fp32 N=32 pair_banks 20x2 want=1 seg_start
+    0xfa301640a1313de9ull,  // edge fp32 N=32 pair_banks 20x2 want=1 seg_row_off
+    0xcd390d0afcd7d4b4ull,  // edge fp32 N=32 pair_banks 20x2 want=1 tcol
+    0x333df5dbfe757981ull,  // edge fp32 N=32 pair_banks 20x2 want=1 src
+    0x071d3dbd65fd335eull,  // edge fp32 N=32 pair_banks 20x2 want=2 scalars
+    0xfc82fec943079b84ull,  // edge fp32 N=32 pair_banks 20x2 want=2 seg_start
+    0xfa301640a1313de9ull,  // edge fp32 N=32 pair_banks 20x2 want=2 seg_row_off
+    0xcd390d0afcd7d4b4ull,  // edge fp32 N=32 pair_banks 20x2 want=2 tcol
+    0x333df5dbfe757981ull,  // edge fp32 N=32 pair_banks 20x2 want=2 src
+    0xefdc22e3ecffcbaaull,  // edge fp32 N=32 pair_banks 20x2 want=auto scalars
+    0x0a5d4b599198d33dull,  // edge fp32 N=32 pair_banks 20x2 want=auto seg_start
+    0xa274f047b9bd7ebdull,  // edge fp32 N=32 pair_banks 20x2 want=auto seg_row_off
+    0x63c2f9cf65b6d8d9ull,  // edge fp32 N=32 pair_banks 20x2 want=auto tcol
+    0x95ccabeff7e270edull,  // edge fp32 N=32 pair_banks 20x2 want=auto src
+    0xa46dd4b38ee6eb0cull,  // edge fp32 N=32 dma 20x2 want=1 scalars
+    0xfc82fec943079b84ull,  // edge fp32 N=32 dma 20x2 want=1 seg_start
+    0xfa301640a1313de9ull,  // edge fp32 N=32 dma 20x2 want=1 seg_row_off
+    0xcd390d0afcd7d4b4ull,  // edge fp32 N=32 dma 20x2 want=1 tcol
+    0x333df5dbfe757981ull,  // edge fp32 N=32 dma 20x2 want=1 src
+    0xa46dd4b38ee6eb0cull,  // edge fp32 N=32 dma 20x2 want=2 scalars
+    0xfc82fec943079b84ull,  // edge fp32 N=32 dma 20x2 want=2 seg_start
+    0xfa301640a1313de9ull,  // edge fp32 N=32 dma 20x2 want=2 seg_row_off
+    0xcd390d0afcd7d4b4ull,  // edge fp32 N=32 dma 20x2 want=2 tcol
+    0x333df5dbfe757981ull,  // edge fp32 N=32 dma 20x2 want=2 src
+    0x18f3356bb1060f3dull,  // edge fp32 N=32 dma 20x2 want=auto scalars
+    0x0a5d4b599198d33dull,  // edge fp32 N=32 dma 20x2 want=auto seg_start
+    0xa274f047b9bd7ebdull,  // edge fp32 N=32 dma 20x2 want=auto seg_row_off
+    0x63c2f9cf65b6d8d9ull,  // edge fp32 N=32 dma 20x2 want=auto tcol
+    0x95ccabeff7e270edull,  // edge fp32 N=32 dma 20x2 want=auto src
+    0xe75d47d98cb8a0a2ull,  // edge fp32 N=32 rowslot 40x5 want=1 scalars
+    0x134b450ae1e4e95dull,  // edge fp32 N=32 rowslot 40x5 want=1 seg_start
+    0x62bcca7e2eff7a7eull,  // edge fp32 N=32 rowslot 40x5 want=1 seg_row_off
+    0x5eadfab72be43d15ull,  // edge fp32 N=32 rowslot 40x5 want=1 tcol
+    0x95b6871224daae71ull,  // edge fp32 N=32 rowslot 40x5 want=1 src
+    0xe75d47d98cb8a0a2ull,  // edge fp32 N=32 rowslot 40x5 want=2 scalars
+    0x134b450ae1e4e95dull,  // edge fp32 N=32 rowslot 40x5 want=2 seg_start
+    0x62bcca7e2eff7a7eull,  // edge fp32 N=32 rowslot 40x5 want=2 seg_row_off
+    0x5eadfab72be43d15ull,  // edge fp32 N=32 rowslot 40x5 want=2 tcol
+    0x95b6871224daae71ull,  // edge fp32 N=32 rowslot 40x5 want=2 src
+    0x242715fe8ac9d06aull,  // edge fp32 N=32 rowslot 40x5 want=auto scalars
+    0xd11f4272cdc9a991ull,  // edge fp32 N=32 rowslot 40x5 want=auto seg_start
+    0x90bca010ffaebd52ull,  // edge fp32 N=32 rowslot 40x5 want=auto seg_row_off
+    0xa3fbed9919d73a67ull,  // edge fp32 N=32 rowslot 40x5 want=auto tcol
+    0x54ee7c4ed81706e9ull,  // edge fp32 N=32 rowslot 40x5 want=auto src
+    0x0b1ac642e0b51857ull,  // edge fp32 N=32 rowslot 64x8 want=1 scalars
+    0xee1c0a01ca124d09ull,  // edge fp32 N=32 rowslot 64x8 want=1 seg_start
+    0xf6a8c2b414fb3810ull,  // edge fp32 N=32 rowslot 64x8 want=1 seg_row_off
+    0x3892f914e73cc495ull,  // edge fp32 N=32 rowslot 64x8 want=1 tcol
+    0x9bc6193a1960b575ull,  // edge fp32 N=32 rowslot 64x8 want=1 src
+    0x0b1ac642e0b51857ull,  // edge fp32 N=32 rowslot 64x8 want=2 scalars
+    0xee1c0a01ca124d09ull,  // edge fp32 N=32 rowslot 64x8 want=2 seg_start
+    0xf6a8c2b414fb3810ull,  // edge fp32 N=32 rowslot 64x8 want=2 seg_row_off
+    0x3892f914e73cc495ull,  // edge fp32 N=32 rowslot 64x8 want=2 tcol
+    0x9bc6193a1960b575ull,  // edge fp32 N=32 rowslot 64x8 want=2 src
+    0x66ffcd642a5d939dull,  // edge fp32 N=32 rowslot 64x8 want=auto scalars
+    0x1eb52246dea82e81ull,  // edge fp32 N=32 rowslot 64x8 want=auto seg_start
+    0x6d46d7b2d50e869dull,  // edge fp32 N=32 rowslot 64x8 want=auto seg_row_off
+    0x74bc3c70045ddbcfull,  // edge fp32 N=32 rowslot 64x8 want=auto tcol
+    0x10638f5d9da020f9ull,  // edge fp32 N=32 rowslot 64x8 want=auto src
 };
 
 static long g_bad = 0;
@@ -176,6 +253,55 @@ static coo make_matrix(uint64_t M, uint64_t K, uint32_t mean) {
     return a;
 }
 
+// The size of the GPU tests' edge pattern (tests/test_gpu_edges.py: 131 x 203), rows of 0..256 entries, from
+// an LCG of its own (the cases above keep their matrices): rows 0, 5, 37, 38, 90 and the three
+// trailing rows empty, row 20 with every column and 53 of them twice (256 entries), row 2 with 40 even
+// columns, rows 10..13 with 1, 7, 8 and 9 entries, rows 1 and 127 with columns 0 and K - 1, the
+// others 2..20 random columns
+static coo make_edge() {
+    const uint64_t M = 131, K = 203;
+    uint64_t lcg = 0x2545f4914f6cdd1dull;
+    auto r32 = [&](uint32_t n) {
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        return (uint32_t)((lcg >> 33) % n);
+    };
+    coo a;
+    a.M = M;
+    a.K = K;
+    for (uint64_t r = 0; r < M; r++) {
+        std::vector<uint64_t> c;
+        const bool empty = r == 0 || r == 5 || r == 37 || r == 38 || r == 90 || r >= 128;
+        if (r == 20) {
+            for (uint64_t x = 0; x < K; x++) c.push_back(x);
+            for (uint64_t x = 0; x < 53; x++) c.push_back((x * 23 + 3) % K);  // 23 and 203 are coprime: 53 distinct
+            std::sort(c.begin(), c.end());
+        } else if (r == 2) {
+            for (uint64_t x = 0; x < 40; x++) c.push_back(4 * x + 2 * (x % 2));
+        } else if (!empty) {
+            const uint32_t n = r >= 10 && r <= 13 ? (r == 10 ? 1u : (uint32_t)(r - 4)) : 2 + r32(19);
+            for (uint32_t i = 0; i < n; i++) c.push_back(r32((uint32_t)K));
+            if (r == 1 || r == 127) {
+                c.push_back(0);
+                c.push_back(K - 1);
+            }
+            std::sort(c.begin(), c.end());
+            c.erase(std::unique(c.begin(), c.end()), c.end());
+        }
+        for (uint64_t x : c) {
+            a.row.push_back(r);
+            a.col.push_back(x);
+        }
+    }
+    a.rp = csr_row_ptr(a.row, M);
+    return a;
+}
+
+// a small integer value per CSR entry, never 0 (the value-level check of lds_case)
+static int64_t value_of(uint64_t e) {
+    const int64_t v = (int64_t)(e * 2654435761ull % 6) - 3;  // -3 .. 2
+    return v >= 0 ? v + 1 : v;                              // -3 .. -1, 1 .. 3
+}
+
 struct blocks {
     std::vector<uint64_t> tb_rows, tb_bmw, bmw_rows;
 };
@@ -194,10 +320,13 @@ static blocks make_blocks(uint64_t M, uint64_t tbr, uint64_t bwr) {
     return b;
 }
 
+// edge: the matrix of make_edge() instead of make_matrix(M, K, 8), with the chunking the case pins
+// (KC columns in nc chunks) instead of the three or more chunks the small budgets of the other cases force
 static void lds_case(const char *name, uint64_t M, uint64_t K, uint64_t tbr, uint64_t bwr, uint32_t N, uint32_t vbytes,
-                     size_t budget, bool dma, uint64_t want) {
+                     size_t budget, bool dma, uint64_t want, const coo *edge = nullptr, uint32_t pin_kc = 0,
+                     uint32_t pin_nc = 0) {
     g_case = name;
-    const coo a = make_matrix(M, K, 8);
+    const coo a = edge ? *edge : make_matrix(M, K, 8);
     const blocks b = make_blocks(M, tbr, bwr);
     EXPECT(M % tbr != 0, "the last BMTB must be short");
     lds_tiles t;
@@ -207,13 +336,18 @@ static void lds_case(const char *name, uint64_t M, uint64_t K, uint64_t tbr, uin
     if (!ok) return;
     const uint64_t nb = b.tb_rows.size() - 1, nnz = a.col.size();
     const bool rowslot = t.maxr == 8, pair_banks = vbytes == 4 && N == 32 && !rowslot;
-    EXPECT(t.nc >= 3 && (uint64_t)t.KC * t.nc >= K && t.KC % 8 == 0, "KC %u x %u chunks", t.KC, t.nc);
+    EXPECT((uint64_t)t.KC * t.nc >= K && t.KC % 8 == 0, "KC %u x %u chunks", t.KC, t.nc);
+    if (edge) EXPECT(t.KC == pin_kc && t.nc == pin_nc, "KC %u x %u chunks, pinned %u x %u", t.KC, t.nc, pin_kc, pin_nc);
+    else EXPECT(t.nc >= 3, "%u chunks", t.nc);
     EXPECT(t.lds_bytes <= budget, "%zu B of LDS over the budget", t.lds_bytes);
     EXPECT(t.rpw_max == tbr && t.waves == (tbr + bwr - 1) / bwr, "rpw_max %u, waves %u", t.rpw_max, t.waves);
     EXPECT(t.seg_start.size() == nb * t.nc + 1 && t.seg_start[0] == 0 && t.seg_start.back() == t.tcol.size() &&
                t.src.size() == t.tcol.size() && t.seg_row_off.size() == nb * t.nc * (t.rpw_max + 1),
            "array sizes");
     std::vector<uint32_t> seen(nnz, 0);
+    // the rows' sums of value x (column + 1) as the kernels walk the tiles: row i of BMTB g over its
+    // [off[i], off[i+1]) of every chunk, a padding entry at value 0
+    std::vector<int64_t> walked(M, 0);
     bool big_row = false, even_row = false;
     for (uint64_t g = 0; g < nb; g++)
         for (uint32_t j = 0; j < t.nc; j++) {
@@ -236,7 +370,10 @@ static void lds_case(const char *name, uint64_t M, uint64_t K, uint64_t tbr, uin
                 for (e1 = e0; e1 < a.rp[r + 1] && a.col[e1] < (uint64_t)(j + 1) * t.KC; e1++) {}
                 std::vector<uint32_t> got;
                 std::vector<unsigned> par;  // column parity per entry, padding included
+                std::vector<uint32_t> padc;  // the padding entries' columns
                 bool all_even = true;
+                // a row without an entry in the chunk gets no padding
+                if (e1 == e0) EXPECT(k1 == k0, "row %llu chunk %u: %u entries of padding alone", (unsigned long long)r, j, k1 - k0);
                 for (uint32_t k = k0; k < k1; k++) {
                     uint32_t c = t.tcol[k];
                     if (rowslot) {
@@ -245,9 +382,10 @@ static void lds_case(const char *name, uint64_t M, uint64_t K, uint64_t tbr, uin
                     }
                     par.push_back(c & 1u);
                     if (t.src[k] == ~0u) {
-                        EXPECT(t.tcol[k] == 0, "padding with a column");
+                        padc.push_back(c);
                         continue;
                     }
+                    if (t.src[k] < nnz) walked[r] += value_of(t.src[k]) * (int64_t)((uint64_t)j * t.KC + c + 1);
                     EXPECT(t.src[k] < nnz, "source entry out of range");
                     if (t.src[k] >= nnz) continue;
                     seen[t.src[k]]++;
@@ -255,6 +393,15 @@ static void lds_case(const char *name, uint64_t M, uint64_t K, uint64_t tbr, uin
                     EXPECT(a.col[t.src[k]] == (uint64_t)j * t.KC + c, "column of entry %u", t.src[k]);
                     all_even &= !(c & 1u);
                 }
+                // padding (value 0) carries a column that an entry of this row in this chunk carries: 0 x a
+                // non-finite B value then stays in a row that holds the column
+                for (uint32_t c : padc) {
+                    bool held = false;
+                    for (uint64_t e = e0; e < e1; e++) held |= a.col[e] == (uint64_t)j * t.KC + c;
+                    EXPECT(held, "row %llu chunk %u: padding with column %u, which the row does not hold there",
+                           (unsigned long long)r, j, c);
+                }
+                EXPECT(padc.size() < 4, "row %llu chunk %u: %zu padding entries", (unsigned long long)r, j, padc.size());
                 std::sort(got.begin(), got.end());
                 EXPECT(got.size() == e1 - e0 && (got.empty() || (got.front() == e0 && got.back() == e1 - 1)),
                        "row %llu chunk %u: entries are not the row's CSR entries", (unsigned long long)r, j);
@@ -288,6 +435,12 @@ static void lds_case(const char *name, uint64_t M, uint64_t K, uint64_t tbr, uin
             }
         }
     for (uint64_t e = 0; e < nnz; e++) EXPECT(seen[e] == 1, "entry %llu placed %u times", (unsigned long long)e, seen[e]);
+    for (uint64_t r = 0; r < M; r++) {
+        int64_t sum = 0;
+        for (uint64_t e = a.rp[r]; e < a.rp[r + 1]; e++) sum += value_of(e) * (int64_t)(a.col[e] + 1);
+        EXPECT(walked[r] == sum, "row %llu: the tiles sum value x (column + 1) to %lld, the CSR to %lld", (unsigned long long)r,
+               (long long)walked[r], (long long)sum);
+    }
     EXPECT(big_row && even_row, "the matrix lacks a > 32-entry row segment or an all-even one");
     hash_array("scalars", std::vector<uint64_t>{t.KC, t.nc, t.RSB, t.rpw_max, t.seg_cap, t.waves, t.maxr, t.lds_bytes});
     hash_array("seg_start", t.seg_start);
@@ -465,6 +618,26 @@ int main(int argc, char **argv) {
         levels_case("merge_path_levels ws=64", l, 64);
         bitmap_case("bitmap rows", s, 8, 0, 0);
         bitmap_case("bitmap rows, sub-matrix", l, 16, 5, 3);
+
+        // the GPU edge pattern's size at the upload's budgets (160 KB; 80 KB with LDS-DMA), K split 1, 2 and
+        // the upload's automatic one (256 / BMTBs, 512 / BMTBs with LDS-DMA): two chunks of 104 columns in one
+        // K range, the same in two, and three of 72 (a fourth would make chunks of under 64).  No K split gives
+        // one chunk here: a chunk is a multiple of 8 columns and build_lds_tiles passes over a chunk wider than
+        // K, so K = 203 never goes as one chunk of 208.  tests/test_gpu_lds_variants.py pins the same table
+        const coo e = make_edge();
+        const struct { const char *name; uint64_t tbr, bwr; uint32_t N, vbytes; bool dma; } kEdge[] = {
+            {"edge fp16 N=8 20x2", 20, 2, 8, 2, false},     {"edge fp32 N=32 pair_banks 20x2", 20, 2, 32, 4, false},
+            {"edge fp32 N=32 dma 20x2", 20, 2, 32, 4, true}, {"edge fp32 N=32 rowslot 40x5", 40, 5, 32, 4, true},
+            {"edge fp32 N=32 rowslot 64x8", 64, 8, 32, 4, true}};
+        for (const auto &c : kEdge) {
+            const uint64_t nbt = (e.M + c.tbr - 1) / c.tbr, wants[3] = {1, 2, (c.dma ? 512u : 256u) / nbt};
+            const uint32_t pins[3][2] = {{104, 2}, {104, 2}, {72, 3}};
+            for (int w = 0; w < 3; w++) {
+                const std::string name = std::string(c.name) + (w == 0 ? " want=1" : w == 1 ? " want=2" : " want=auto");
+                lds_case(name.c_str(), e.M, e.K, c.tbr, c.bwr, c.N, c.vbytes, (c.dma ? 80 : 160) * 1024, c.dma, wants[w], &e,
+                         pins[w][0], pins[w][1]);
+            }
+        }
     } catch (const std::exception &e) {
         std::fprintf(stderr, "%s: %s\n", g_case.c_str(), e.what());
         return 2;

@@ -202,9 +202,9 @@ def test_sparse_linear_grad_modes_without_a_gpu():
 
 def test_the_sanitizer_program_of_the_pattern_builder():
     """tools/sddmm_layout_check.cc, a stand-alone program, built with the Makefile's SANFLAGS (ASan + UBSan on
-    the host objects) and run: hand-written patterns against tables.  It is part of `make san_check` and runs
-    there before tools/gather_layout_check.cc; the whole target is not run here, because that older program
-    has failed since the gather layouts' padding columns changed (its expectations were not updated)."""
+    the host objects) and run: hand-written patterns against tables.  It is part of `make san_check`; the
+    whole target, tools/gather_layout_check.cc included (its expectations follow the gather layouts' padding
+    columns again), runs in tests/test_san_check.py."""
     dry = subprocess.run(["make", "-n", "-B", "-C", CSRC, "san_check"], capture_output=True, text=True, check=True).stdout
     assert "./build_san/sddmm_layout_check" in dry
     link = [ln for ln in dry.splitlines() if "-o build_san/sddmm_layout_check" in ln]
