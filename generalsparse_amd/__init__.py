@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import GS_BF16, GS_F16, GS_F32, GS_W_FP8_E4M3, GS_W_NATIVE, GsError
 
-__all__ = ["Plan", "Batch", "Rotation", "SparseLinear", "set_config", "GsError", "GS_F16", "GS_F32", "GS_BF16", "PIPELINES", "load_library",
+__all__ = ["Plan", "Batch", "LinearBatch", "Rotation", "SparseLinear", "SparseLinearGroup", "set_config", "GsError", "GS_F16", "GS_F32", "GS_BF16", "PIPELINES", "load_library",
            "convert_values", "GS_W_NATIVE", "GS_W_FP8_E4M3", "fp8_quantize", "fp8_decode", "sddmm_geometry"]
 
 # token_test.cc pipelines (+ the two compositions this engine adds)
@@ -299,6 +299,113 @@ class Batch:
         return [out[i] for i in range(min(k, cap))]
 
 
+def _check_linear_operands(info, x, out):
+    """Plan.linear's operands: x a contiguous (n, K) GPU tensor of the plan's dtype, n >= 1; out (or None) a
+    contiguous (n, M) tensor of that dtype on x's device.  Returns (dtype, n, M)"""
+    want, M, K = _torch_dtype(info["dtype"]), info["rows"], info["cols"]
+    if not (x.is_cuda and x.dim() == 2 and x.is_contiguous()):
+        raise ValueError("x must be a contiguous 2-D GPU tensor")
+    if x.shape[1] != K:
+        raise ValueError(f"x has {x.shape[1]} columns, A has {K} columns")
+    if x.dtype != want:
+        raise TypeError(f"x must be {want}")
+    n = int(x.shape[0])
+    if n < 1:
+        raise ValueError("x holds no token")
+    if out is not None and not (out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == want
+                                and tuple(out.shape) == (n, M)):
+        raise ValueError(f"out must be a contiguous {want} tensor of shape ({n}, {M}) on {x.device}")
+    return want, n, M
+
+
+class LinearBatch:
+    """a fixed list of linear calls (plan, replica, x, out), each what Plan.linear(x, out, replica) is, run by
+    gs_linear_batch: consecutive entries that are each ONE k_mfma_ks_tm launch of one instantiation run as one
+    grouped launch (k_mfma_ks_tm_group) -- every entry with its own token count, several may share one x --
+    and every other entry through Plan.linear's own path.  An entry's out has the bits of its own
+    Plan.linear call.  epilogues: per entry None or a dict with any of alpha / bias / activation / residual
+    (Plan.linear's keywords).  The operands are checked and the argument arrays built here, once, before
+    anything touches a device; run() enqueues the whole batch on a stream.  Entries that share a plan
+    object need distinct replicas to share a launch (Plan.add_replica); launches() tells."""
+
+    def __init__(self, entries, epilogues=None):
+        entries = [tuple(e) for e in entries]
+        n = len(entries)
+        if any(len(e) != 4 for e in entries):
+            raise ValueError("an entry is (plan, replica, x, out)")
+        if epilogues is not None:
+            if len(epilogues) != n:
+                raise ValueError("epilogues must hold one item (None or a dict) per entry")
+            for ep in epilogues:
+                if ep is not None:
+                    unknown = set(ep) - set(_EPILOGUE_KEYS)
+                    if unknown:
+                        raise ValueError(f"unknown epilogue keys {sorted(unknown)}")
+                    _check_activation(ep.get("activation"))
+        eps, tokens = [], []
+        for i, (plan, replica, x, out) in enumerate(entries):
+            info = plan.info()
+            if not 0 <= int(replica) < max(1, info["replicas"]):
+                raise ValueError(f"entry {i}: replica {replica} of a plan with {info['replicas']}")
+            if out is None:
+                raise ValueError(f"entry {i}: out must be a tensor (the batch allocates nothing)")
+            _, tok, _ = _check_linear_operands(info, x, out)
+            tokens.append(tok)
+            ep = epilogues[i] if epilogues is not None else None
+            eps.append(_epilogue(info, x.device, out, tok, token_major=True, **ep) if ep is not None else None)
+        self._L = _lib.load()
+        self.entries, self._keep, self._eps = entries, epilogues, eps  # keeps plans, operands, bias and residual alive
+        self._epi = None
+        if any(e is not None for e in eps):
+            self._epi = (ctypes.POINTER(_lib.GsEpilogue) * n)(*[ctypes.pointer(e) if e is not None else None for e in eps])
+        self._p = (ctypes.c_void_p * n)(*[e[0]._h for e in entries])
+        self._r = (ctypes.c_int * n)(*[int(e[1]) for e in entries])
+        self._x = (ctypes.c_void_p * n)(*[e[2].data_ptr() for e in entries])
+        self._y = (ctypes.c_void_p * n)(*[e[3].data_ptr() for e in entries])
+        self._t = (ctypes.c_int * n)(*tokens)
+        self.n = n
+        self._dev = entries[0][2].device if n else None
+
+    def run(self, stream=None):
+        if self.n == 0:
+            return
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self._dev).cuda_stream
+        _lib.check(self._L.gs_linear_batch(self._p, self._r, self._x, self._y, self._t, self._epi, self.n,
+                                           ctypes.c_void_p(stream)))
+
+    def launches(self):
+        """entries per launch, as run() enqueues them (gs_linear_batch_launches): a grouped k_mfma_ks_tm_group
+        launch carries up to 32 entries; an entry that runs through Plan.linear's path counts as 1"""
+        cap = max(1, self.n)
+        out = (ctypes.c_int * cap)()
+        k = self._L.gs_linear_batch_launches(self._p, self._r, self._x, self._t, self.n, out, cap)
+        if k < 0:
+            _lib.check(k)
+        return [out[i] for i in range(min(k, cap))]
+
+
+def linear_group_layout(nwg, tiles):
+    """begin[] of one grouped token-major launch, host only (gs_linear_group_layout): entry i with nwg[i]
+    workgroups per token tile and tiles[i] tiles owns workgroups [begin[i], begin[i] + nwg[i] * tiles[i]); every
+    begin is a multiple of 8, begin[-1] is the grid.  Refused: no entry, more than linear_group_max(), an entry
+    without workgroups, a grid past 2^31 - 1"""
+    n = len(nwg)
+    if len(tiles) != n:
+        raise ValueError("nwg and tiles must have one length")
+    a = (ctypes.c_uint32 * max(1, n))(*[int(v) for v in nwg])
+    t = (ctypes.c_uint32 * max(1, n))(*[int(v) for v in tiles])
+    out = (ctypes.c_uint32 * (n + 1))()
+    _lib.check(_lib.load().gs_linear_group_layout(a, t, n, out))
+    return list(out)
+
+
+def linear_group_max():
+    """the most entries of one grouped token-major launch (gs_linear_group_max)"""
+    return int(_lib.load().gs_linear_group_max())
+
+
 class Rotation:
     """`count` SpMMs of one plan from native code (gs_spmm_rotate), rotating its replicas and
     a fixed list of (B, C) pairs: launch i uses pair (first + i) % len(Bs).  The operands are
@@ -517,19 +624,7 @@ class Plan:
         _check_activation(activation)
         import torch
         info = self.info()
-        want, M, K = _torch_dtype(info["dtype"]), info["rows"], info["cols"]
-        if not (x.is_cuda and x.dim() == 2 and x.is_contiguous()):
-            raise ValueError("x must be a contiguous 2-D GPU tensor")
-        if x.shape[1] != K:
-            raise ValueError(f"x has {x.shape[1]} columns, A has {K} columns")
-        if x.dtype != want:
-            raise TypeError(f"x must be {want}")
-        n = int(x.shape[0])
-        if n < 1:
-            raise ValueError("x holds no token")
-        if out is not None and not (out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == want
-                                    and tuple(out.shape) == (n, M)):
-            raise ValueError(f"out must be a contiguous {want} tensor of shape ({n}, {M}) on {x.device}")
+        want, n, M = _check_linear_operands(info, x, out)
         epi = _epilogue(info, x.device, out, n, alpha, bias, activation, residual, token_major=True)
         if out is None:
             out = torch.empty((n, M), dtype=want, device=x.device)
@@ -796,8 +891,8 @@ class Plan:
 
 
 def __getattr__(name):
-    """SparseLinear lives in generalsparse_amd.nn, which needs torch: imported on first use"""
-    if name == "SparseLinear":
-        from .nn import SparseLinear
-        return SparseLinear
+    """SparseLinear and SparseLinearGroup live in generalsparse_amd.nn, which needs torch: imported on first use"""
+    if name in ("SparseLinear", "SparseLinearGroup"):
+        from . import nn
+        return getattr(nn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

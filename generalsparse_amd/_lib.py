@@ -64,6 +64,14 @@ SIGNATURES = {
     "gs_plan_linear_launches": ([ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
     "gs_linear_tile_split": ([ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
                               ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
+    "gs_linear_batch": ([ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
+                         ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
+                         ctypes.POINTER(ctypes.POINTER(GsEpilogue)), ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "gs_linear_batch_launches": ([ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
+                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
+    "gs_linear_group_layout": ([u32p, u32p, ctypes.c_int, u32p], ctypes.c_int),
+    "gs_linear_group_max": ([], ctypes.c_int),
     "gs_plan_pattern": ([ctypes.c_void_p, u64p, u64p, f32p, ctypes.c_uint64, u64p], ctypes.c_int),
     "gs_plan_values_prepare": ([ctypes.c_void_p], ctypes.c_int),
     "gs_plan_set_values": ([ctypes.c_void_p, ctypes.c_void_p, f32p, ctypes.c_void_p], ctypes.c_int),

@@ -22,6 +22,8 @@ constexpr int kMfmaBWavesG = 2, kMfmaAWavesG = 8;
 
 // k_mfma_ks_group: entries of one grouped launch (kernel arguments, ~3.9 KB of the 4 KB)
 constexpr int kKsGroupMax = 32;
+// k_mfma_ks_tm_group (gs_linear_batch): likewise, 32 entries of 120 B + the first workgroups
+constexpr int kKsTmGroupMax = 32;
 
 // The element-wise epilogue of one SpMM (gs_epilogue of include/generalsparse.h, the same 24 bytes;
 // the stages and their order: epilogue_apply, kernel_common.hpp).  A kernel argument of k_mfma_ks,

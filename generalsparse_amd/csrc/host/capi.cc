@@ -381,8 +381,9 @@ linear_ks_state &ensure_linear_ks(gs_plan *p, int replica, uint32_t T, hipStream
 // epoch bit between launches and the slabs the last epoch's tagged words, both laid out by T: where
 // the state may hold another layout's (another T before, or a captured launch that replays at any
 // time) the region this T uses is zeroed on the stream ahead of the launch
-void launch_linear_tiles(gs_plan *p, int replica, linear_ks_state &l, const void *X, void *Y, uint32_t n, uint32_t T,
-                         hipStream_t s, const gsk::epilogue &e) {
+// (linear_ks_ready: the state made ready for a launch of T tiles -- returns its counters; the caller sets
+// l.last = T once the launch is enqueued.  Shared with gs_linear_batch's grouped launches)
+uint32_t *linear_ks_ready(gs_plan *p, linear_ks_state &l, uint32_t T, hipStream_t s) {
     const gs::device_plan &d = p->st.dev;
     const size_t slab = (size_t)d.n_rows_aux * d.ksplit * d.maxr * 2048u, nctr = (size_t)d.n_rows_aux * T;
     GS_CHECK(l.buf && T <= l.cap, "gs_linear: K-split state smaller than the launch");
@@ -394,6 +395,11 @@ void launch_linear_tiles(gs_plan *p, int replica, linear_ks_state &l, const void
         GS_HIP(hipMemsetAsync(arrivals, 0, nctr * sizeof(uint32_t), s));
     }
     l.last = 0;  // (unknown if the launch throws)
+    return arrivals;
+}
+void launch_linear_tiles(gs_plan *p, int replica, linear_ks_state &l, const void *X, void *Y, uint32_t n, uint32_t T,
+                         hipStream_t s, const gsk::epilogue &e) {
+    uint32_t *arrivals = linear_ks_ready(p, l, T, s);
     gs::launch_linear_fused(p->st, replica, X, Y, n, s, e, (float *)l.buf, arrivals);
     l.last = T;
 }
@@ -1142,58 +1148,171 @@ int gs_plan_epilogue_fused(gs_plan_t *p, int N) {
     return rc < 0 ? rc : fused;
 }
 
-int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, const gs_epilogue *epi, gs_stream_t stream) {
-    return guard([&] {
-        GS_CHECK(p && X && Y && n_tokens >= 1, "bad argument");
-        // every check before any launch: gs_spmm_ex's, the replica and the residual's whole extent too
-        auto ks = kernel_states(p);
-        for (gs::plan_state *s : ks) {
-            GS_CHECK(s->uploaded, "plan is not on the device");
-            GS_CHECK(replica >= 0 && (size_t)replica < s->dev.replicas.size(), "bad replica index");
-        }
-        gsk::epilogue e = gsk::epilogue_identity();
-        checked_epilogue(epi, Y, &e);
-        const int dtype = ks.front()->dev.dtype;
-        const size_t eb = gs::elem_bytes(dtype);
-        const uint32_t N = (uint32_t)n_tokens;
-        if (e.residual) {
-            const uintptr_t bytes = (uintptr_t)p->st.M * N * eb, r = (uintptr_t)e.residual, y = (uintptr_t)Y;
-            GS_CHECK(r + bytes <= y || y + bytes <= r, "gs_epilogue: the residual may not overlap Y");
-        }
-        hipStream_t s = (hipStream_t)stream;
-        if (linear_fused(p, N) && (uintptr_t)X % 16 == 0) {
-            // k_mfma_ks_tm on 32-token tiles: one launch, or several in token order where the tiles'
-            // K-split state would pass LINEAR_WS_KB.  A launch of one tile (the plan's own width, a
-            // remainder) runs on the upload's state; the state of the others is there before the first
-            const std::vector<uint32_t> tiles = linear_tiles(p, N);
-            const uint32_t most = *std::max_element(tiles.begin(), tiles.end());
-            linear_ks_state *ks_state = p->st.dev.ksplit > 1 && most > 1 ? &ensure_linear_ks(p, replica, most, s) : nullptr;
-            uint32_t tok = 0;
-            for (uint32_t T : tiles) {
-                const uint32_t n = std::min(N - tok, T * 32u);
-                const void *x = (const char *)X + (size_t)tok * p->st.K * eb;
-                void *y = (char *)Y + (size_t)tok * p->st.M * eb;
-                gsk::epilogue et = e;  // (the bias is per output feature: not offset)
-                if (e.residual) et.residual = (const char *)e.residual + (size_t)tok * p->st.M * eb;
-                if (ks_state && T > 1) launch_linear_tiles(p, replica, *ks_state, x, y, n, T, s, et);
-                else gs::launch_linear_fused(p->st, replica, x, y, n, s, et);
-                tok += n;
-            }
-            return;
-        }
-        // every other plan, width and alignment: X -> B (K x N), the plan's launches into C (M x N),
-        // the epilogue and the way back in k_tm_out
-        // (FP8 weights: the SpMM in the middle runs at the plan's width only -- refused before any launch)
-        GS_CHECK(p->st.dev.weights != gs::kWFp8 || N == p->st.dev.lds_N,
+namespace {
+// gs_linear's checks, all of them before any launch (gs_linear_batch: of every entry before the first):
+// gs_spmm_ex's, the replica and the residual's whole extent too.  Returns the call's epilogue
+gsk::epilogue check_linear(gs_plan *p, int replica, const void *X, void *Y, int n_tokens, const gs_epilogue *epi) {
+    GS_CHECK(p && X && Y && n_tokens >= 1, "bad argument");
+    auto ks = kernel_states(p);
+    for (gs::plan_state *s : ks) {
+        GS_CHECK(s->uploaded, "plan is not on the device");
+        GS_CHECK(replica >= 0 && (size_t)replica < s->dev.replicas.size(), "bad replica index");
+    }
+    gsk::epilogue e = gsk::epilogue_identity();
+    checked_epilogue(epi, Y, &e);
+    if (e.residual) {
+        const uintptr_t bytes = (uintptr_t)p->st.M * (uint32_t)n_tokens * gs::elem_bytes(ks.front()->dev.dtype);
+        const uintptr_t r = (uintptr_t)e.residual, y = (uintptr_t)Y;
+        GS_CHECK(r + bytes <= y || y + bytes <= r, "gs_epilogue: the residual may not overlap Y");
+    }
+    // (FP8 weights on the three-launch path: the SpMM in the middle runs at the plan's width only)
+    if (!(linear_fused(p, (uint32_t)n_tokens) && (uintptr_t)X % 16 == 0))
+        GS_CHECK(p->st.dev.weights != gs::kWFp8 || (uint32_t)n_tokens == p->st.dev.lds_N,
                  "gs_linear: a plan with FP8 weights takes the three-launch path (misaligned x, LINEAR_FUSE = 0) at the "
                  "token count it was built for (" + std::to_string(p->st.dev.lds_N) + ") only");
-        linear_scratch &l = ensure_linear(p, replica, N, eb, ks.front()->dev.device, s);
-        void *B = l.buf, *C = (char *)l.buf + linear_c_offset(p->st.K, N, eb);
-        gs::launch_tm_in(X, B, p->st.K, N, dtype, s);
-        spmm_all(p, replica, B, C, N, s, nullptr);
-        gs::launch_tm_out(C, Y, p->st.M, N, dtype, e, s);
+    return e;
+}
+
+// gs_linear's launches on checked arguments (gs_linear_batch: an entry that runs alone)
+void run_linear(gs_plan *p, int replica, const void *X, void *Y, uint32_t N, const gsk::epilogue &e, hipStream_t s) {
+    const int dtype = kernel_states(p).front()->dev.dtype;
+    const size_t eb = gs::elem_bytes(dtype);
+    if (linear_fused(p, N) && (uintptr_t)X % 16 == 0) {
+        // k_mfma_ks_tm on 32-token tiles: one launch, or several in token order where the tiles'
+        // K-split state would pass LINEAR_WS_KB.  A launch of one tile (the plan's own width, a
+        // remainder) runs on the upload's state; the state of the others is there before the first
+        const std::vector<uint32_t> tiles = linear_tiles(p, N);
+        const uint32_t most = *std::max_element(tiles.begin(), tiles.end());
+        linear_ks_state *ks_state = p->st.dev.ksplit > 1 && most > 1 ? &ensure_linear_ks(p, replica, most, s) : nullptr;
+        uint32_t tok = 0;
+        for (uint32_t T : tiles) {
+            const uint32_t n = std::min(N - tok, T * 32u);
+            const void *x = (const char *)X + (size_t)tok * p->st.K * eb;
+            void *y = (char *)Y + (size_t)tok * p->st.M * eb;
+            gsk::epilogue et = e;  // (the bias is per output feature: not offset)
+            if (e.residual) et.residual = (const char *)e.residual + (size_t)tok * p->st.M * eb;
+            if (ks_state && T > 1) launch_linear_tiles(p, replica, *ks_state, x, y, n, T, s, et);
+            else gs::launch_linear_fused(p->st, replica, x, y, n, s, et);
+            tok += n;
+        }
+        return;
+    }
+    // every other plan, width and alignment: X -> B (K x N), the plan's launches into C (M x N),
+    // the epilogue and the way back in k_tm_out
+    linear_scratch &l = ensure_linear(p, replica, N, eb, kernel_states(p).front()->dev.device, s);
+    void *B = l.buf, *C = (char *)l.buf + linear_c_offset(p->st.K, N, eb);
+    gs::launch_tm_in(X, B, p->st.K, N, dtype, s);
+    spmm_all(p, replica, B, C, N, s, nullptr);
+    gs::launch_tm_out(C, Y, p->st.M, N, dtype, e, s);
+}
+
+// the launches of a linear batch (gs_linear_batch), plan_batch's rule on ks_tm_group_key: runs of consecutive
+// entries that are one grouped k_mfma_ks_tm launch (equal key != 0; up to kKsTmGroupMax, each (plan, replica)
+// once), single gs_linear calls otherwise.  Checks what the key reads: the plan, its upload, the replica
+struct linear_batch_launch {
+    uint32_t key;
+    std::vector<int> idx;
+};
+std::vector<linear_batch_launch> plan_linear_batch(gs_plan_t *const *plans, const int *replicas, const void *const *X,
+                                                   const int *n_tokens, int n) {
+    std::vector<linear_batch_launch> out;
+    for (int i = 0; i < n; i++) {
+        gs_plan *p = plans[i];
+        GS_CHECK(p && n_tokens[i] >= 1, "bad batch entry " + std::to_string(i));
+        for (gs::plan_state *s : kernel_states(p)) {
+            GS_CHECK(s->uploaded, "batch entry " + std::to_string(i) + ": plan is not on the device");
+            GS_CHECK(replicas[i] >= 0 && (size_t)replicas[i] < s->dev.replicas.size(),
+                     "batch entry " + std::to_string(i) + ": bad replica index");
+        }
+        const uint32_t k = divided(p) ? 0u : gs::ks_tm_group_key(p->st, (uint32_t)n_tokens[i], X[i]);
+        bool join = k != 0 && !out.empty() && out.back().key == k && out.back().idx.size() < (size_t)gsk::kKsTmGroupMax;
+        if (join)  // a (plan, replica) twice in one grid would share tickets and slabs
+            for (int j : out.back().idx) join &= !(plans[j] == p && replicas[j] == replicas[i]);
+        if (join)
+            out.back().idx.push_back(i);
+        else
+            out.push_back({k, {i}});
+    }
+    return out;
+}
+}  // namespace
+
+int gs_linear(gs_plan_t *p, int replica, const void *X, void *Y, int n_tokens, const gs_epilogue *epi, gs_stream_t stream) {
+    return guard([&] {
+        const gsk::epilogue e = check_linear(p, replica, X, Y, n_tokens, epi);
+        run_linear(p, replica, X, Y, (uint32_t)n_tokens, e, (hipStream_t)stream);
     });
 }
+
+int gs_linear_batch(gs_plan_t *const *plans, const int *replicas, const void *const *X, void *const *Y, const int *n_tokens,
+                    const gs_epilogue *const *epi, int n, gs_stream_t stream) {
+    return guard([&] {
+        GS_CHECK(plans && replicas && X && Y && n_tokens && n >= 0, "bad argument");
+        hipStream_t s = (hipStream_t)stream;
+        // every check of every entry before the first launch: a refused call leaves every Y untouched
+        std::vector<gsk::epilogue> ep((size_t)n, gsk::epilogue_identity());
+        for (int i = 0; i < n; i++) {
+            GS_CHECK(plans[i] && X[i] && Y[i] && n_tokens[i] >= 1, "bad batch entry " + std::to_string(i));
+            try {
+                ep[(size_t)i] = check_linear(plans[i], replicas[i], X[i], Y[i], n_tokens[i], epi ? epi[i] : nullptr);
+            } catch (const gs::gs_error &e) {  // gs_linear's message, with the entry it is about
+                throw gs::gs_error("batch entry " + std::to_string(i) + ": " + e.what(), e.code);
+            }
+        }
+        const auto launches = plan_linear_batch(plans, replicas, X, n_tokens, n);
+        // the K-split state of the grouped entries with K ranges and more than one tile, allocated (first use, a
+        // larger tile count) before the first launch as well
+        auto tiles_of = [&](int i) { return ((uint32_t)n_tokens[i] + 31u) / 32u; };
+        auto own_state = [&](int i) { return plans[i]->st.dev.ksplit > 1 && tiles_of(i) > 1; };
+        for (const linear_batch_launch &l : launches)
+            for (int i : l.idx)
+                if (l.idx.size() > 1 && own_state(i)) ensure_linear_ks(plans[i], replicas[i], tiles_of(i), s);
+        for (const linear_batch_launch &l : launches) {
+            if (l.idx.size() == 1) {  // gs_linear's own code: the same bits, the same three-launch fallback
+                const int i = l.idx[0];
+                run_linear(plans[i], replicas[i], X[i], Y[i], (uint32_t)n_tokens[i], ep[(size_t)i], s);
+                continue;
+            }
+            // one k_mfma_ks_tm_group launch; the epilogues in the kernel, as k_mfma_ks_tm applies them
+            std::vector<gs::ks_tm_group_item> grp;
+            for (int i : l.idx) {
+                gs::ks_tm_group_item it{&plans[i]->st, replicas[i], X[i], Y[i], (uint32_t)n_tokens[i], ep[(size_t)i]};
+                if (own_state(i)) {  // launch_linear_tiles' rule: zeroed where the state may hold another layout's
+                    linear_ks_state &st = plans[i]->lin_ks[(size_t)replicas[i]];
+                    it.arrivals = linear_ks_ready(plans[i], st, tiles_of(i), s);
+                    it.slabs = (float *)st.buf;
+                }
+                grp.push_back(it);
+            }
+            gs::launch_ks_tm_group(grp, s);
+            for (int i : l.idx)
+                if (own_state(i)) plans[i]->lin_ks[(size_t)replicas[i]].last = tiles_of(i);
+        }
+    });
+}
+
+int gs_linear_batch_launches(gs_plan_t *const *plans, const int *replicas, const void *const *X, const int *n_tokens, int n,
+                             int *entries_per_launch, int cap) {
+    int count = 0;
+    const int rc = guard([&] {
+        GS_CHECK(plans && replicas && X && n_tokens && n >= 0 && cap >= 0 && (cap == 0 || entries_per_launch), "bad argument");
+        const auto ls = plan_linear_batch(plans, replicas, X, n_tokens, n);
+        count = (int)ls.size();
+        for (int i = 0; i < count && i < cap; i++) entries_per_launch[i] = (int)ls[(size_t)i].idx.size();
+    });
+    return rc < 0 ? rc : count;
+}
+
+int gs_linear_group_layout(const uint32_t *nwg, const uint32_t *tiles, int n, uint32_t *begin) {
+    return guard([&] {
+        GS_CHECK(nwg && tiles && begin && n >= 1, "bad argument");
+        GS_CHECK(n <= gsk::kKsTmGroupMax, "gs_linear_group_layout: more than " + std::to_string(gsk::kKsTmGroupMax) + " entries");
+        GS_CHECK(gs::ks_tm_group_layout(nwg, tiles, (size_t)n, begin),
+                 "gs_linear_group_layout: an entry without workgroups, or a grid past 2^31 - 1 workgroups");
+    });
+}
+
+int gs_linear_group_max(void) { return gsk::kKsTmGroupMax; }
 
 int gs_plan_pattern(gs_plan_t *p, uint64_t *row, uint64_t *col, float *val, uint64_t cap, uint64_t *nnz) {
     return guard([&] {

@@ -146,6 +146,22 @@ inline std::vector<uint32_t> ks_tm_tile_split(uint32_t n_tokens, uint32_t cap) {
     for (uint32_t left = (n_tokens + 31u) / 32u; left; left -= out.back()) out.push_back(std::min(left, cap));
     return out;
 }
+// the grid of one k_mfma_ks_tm_group launch (gs_linear_batch): entry i of n owns workgroups [begin[i], begin[i] +
+// nwg[i] * tiles[i]); every begin is rounded up to a multiple of 8 (the entry's block numbers keep the XCD residues
+// xcd_block assumes; the workgroups in between exit at once) and begin[n] is the grid.  False -- begin untouched --
+// for no entry, more than kKsTmGroupMax, an entry without workgroups or a grid past 2^31 - 1
+inline bool ks_tm_group_layout(const uint32_t *nwg, const uint32_t *tiles, size_t n, uint32_t *begin) {
+    if (n < 1 || n > (size_t)gsk::kKsTmGroupMax) return false;
+    uint64_t at[gsk::kKsTmGroupMax + 1] = {0};
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t wg = (uint64_t)nwg[i] * tiles[i];
+        if (wg < 1 || wg > 0x7fffffffull) return false;
+        at[i + 1] = i + 1 < n ? (at[i] + wg + 7u) & ~7ull : at[i] + wg;
+        if (at[i + 1] > 0x7fffffffull) return false;
+    }
+    for (size_t i = 0; i <= n; i++) begin[i] = (uint32_t)at[i];
+    return true;
+}
 
 bool build_ks_tiles(const std::vector<uint64_t> &tb_rows, const std::vector<uint32_t> &row_ptr,
                     const std::vector<uint64_t> &col, const std::vector<float> &vals, uint64_t K, uint32_t N,

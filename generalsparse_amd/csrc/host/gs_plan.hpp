@@ -217,6 +217,24 @@ struct ks_group_item {
 };
 uint32_t ks_group_key(const plan_state &p, uint32_t N);  // 0: not groupable
 void launch_ks_group(const std::vector<ks_group_item> &it, uint32_t N, hipStream_t s);
+// grouped k_mfma_ks_tm launches (gs_linear_batch; ks_tm_group_launch.hip): one grid over up to kKsTmGroupMax
+// entries of one instantiation (equal nonzero ks_tm_group_key), every entry a distinct (plan, replica) with its
+// own token count.  slabs / arrivals: launch_linear_fused's -- K-split state laid out for the entry's
+// ceil(n_tokens / 32) tiles where the plan has K ranges and the entry more than one tile, null otherwise
+struct ks_tm_group_item {
+    const plan_state *p;
+    int replica;
+    const void *X;
+    void *Y;
+    uint32_t n_tokens;
+    gsk::epilogue epi = gsk::epilogue_identity();  // applied in the kernel (store_item)
+    float *slabs = nullptr;
+    uint32_t *arrivals = nullptr;
+};
+// 0: not groupable.  Nonzero (dtype, NT, RT, MAXG) where gs_linear would run this call as a single k_mfma_ks_tm
+// launch of 16-bit values: linear_fuses, X 16-byte aligned, native weights, one launch under LINEAR_WS_KB
+uint32_t ks_tm_group_key(const plan_state &p, uint32_t n_tokens, const void *X);
+void launch_ks_tm_group(const std::vector<ks_tm_group_item> &it, hipStream_t s);
 // sddmm_launch.hip: k_sddmm_tm (gs_sddmm).  out[e] = sum over t < n of G[t][row_e] * X[t][col_e] for the
 // entries of the CSR pattern rp (M + 1 u32) / cols (col_bytes 2: u16, 4: u32) in canonical order
 // (sddmm_layout.hpp); G: n x M, X: n x K of dtype (kF16 / kBF16), out: fp32.  Allocates nothing

@@ -1,5 +1,5 @@
 // kernels/ks_dispatch.hpp -- what the launch files of the k_mfma_ks family (ks_launch.hip, ks_w8_launch.hip,
-// ks_tm_launch.hip) share: the object selection of the files built more than once, the dispatch from a plan's
+// ks_tm_launch.hip, ks_tm_group_launch.hip) share: the object selection of the files built more than once, the dispatch from a plan's
 // run-time values to template arguments, the prio word and the release-layout predicate.  Host code only.
 #pragma once
 
@@ -7,7 +7,7 @@
 
 #include <type_traits>
 
-// ks_launch.hip and ks_tm_launch.hip are built once per value (Makefile, NAME_SRC): the fp16 instantiations
+// ks_launch.hip, ks_tm_launch.hip and ks_tm_group_launch.hip are built once per value (Makefile, NAME_SRC): the fp16 instantiations
 // with every entry point, the bf16 twins, and (ks_tm_launch.hip) the FP8-weight forms, each set of kernels
 // in an object of its own so that they compile in parallel
 #define GS_KS_F16 0

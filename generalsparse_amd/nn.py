@@ -21,7 +21,7 @@ until a sync_values() with host=True).  sync_values(rebuild=True) is the host-si
 import numpy as np
 import torch
 
-from . import GS_W_FP8_E4M3, GsError, Plan, _check_activation, _dtype_code, _torch_dtype, _weights_code
+from . import GS_W_FP8_E4M3, GsError, LinearBatch, Plan, _check_activation, _dtype_code, _torch_dtype, _weights_code
 
 GRAD_MODES = (None, "input", "all")
 
@@ -239,6 +239,18 @@ class SparseLinear(torch.nn.Module):
     def forward(self, x, residual=None):
         """x: (..., in_features) of the plan's dtype on its device -> (..., out_features); the leading
         dimensions are flattened into the token count.  residual: (..., out_features), added last."""
+        lead, x2, residual = self._flatten(x, residual)
+        if self._wants_grad(x2, residual):
+            values = self.values if self.grad == "all" else None
+            y = _SparseLinearFn.apply(x2, residual, values, self.bias, self)
+            return y.reshape(lead + (self.out_features,))
+        bias = self.bias.detach() if isinstance(self.bias, torch.nn.Parameter) else self.bias
+        y = self.plan.linear(x2, bias=bias, activation=self.activation, residual=residual)
+        return y.reshape(lead + (self.out_features,))
+
+    def _flatten(self, x, residual):
+        """forward's operands as Plan.linear takes them: (leading shape, x as (n, in), residual as (n, out) or
+        None), after forward's refusals"""
         if self.grad is None and torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("SparseLinear is inference only (no backward pass): run it under torch.no_grad() "
                                "or on a tensor that does not require grad")
@@ -254,14 +266,14 @@ class SparseLinear(torch.nn.Module):
             residual = residual.reshape(-1, self.out_features)
             if not residual.is_contiguous():
                 residual = residual.contiguous()
-        if self.grad is not None and torch.is_grad_enabled():
-            values = self.values if self.grad == "all" else None
-            if any(t is not None and t.requires_grad for t in (x2, residual, values, self.bias)):
-                y = _SparseLinearFn.apply(x2, residual, values, self.bias, self)
-                return y.reshape(lead + (self.out_features,))
-        bias = self.bias.detach() if isinstance(self.bias, torch.nn.Parameter) else self.bias
-        y = self.plan.linear(x2, bias=bias, activation=self.activation, residual=residual)
-        return y.reshape(lead + (self.out_features,))
+        return lead, x2, residual
+
+    def _wants_grad(self, x2, residual):
+        """forward goes through autograd (_SparseLinearFn): grad is enabled and an operand asks for it"""
+        if self.grad is None or not torch.is_grad_enabled():
+            return False
+        values = self.values if self.grad == "all" else None
+        return any(t is not None and t.requires_grad for t in (x2, residual, values, self.bias))
 
     def extra_repr(self):
         info = self.plan.info()
@@ -277,3 +289,49 @@ class SparseLinear(torch.nn.Module):
             if info["weights"] == GS_W_FP8_E4M3:
                 s += ", weights=fp8_e4m3"
         return s
+
+
+class SparseLinearGroup(torch.nn.Module):
+    """several SparseLinear layers run as one call (LinearBatch, gs_linear_batch): the Q/K/V projections of one
+    x, an MLP's gate / up pair, experts with their own inputs and token counts.  layers: SparseLinear modules
+    (kept as a ModuleList).  forward returns the list of their outputs, each with the bits of the layer's own
+    forward.  Layers whose calls are each one k_mfma_ks_tm launch of one instantiation share ONE grouped
+    launch; every other layer runs inside the same call through its own path (LinearBatch.launches tells).
+    Each layer's bias and activation are its entry's epilogue.
+    When grad is enabled and any input, residual, layer.values or layer.bias requires grad, the layers are
+    called one by one, so autograd works as for the single layer; a grad=None layer refuses an input that
+    requires grad, as alone.  Layers that share a plan object would share its replica 0 -- its K-split tickets
+    and slabs -- so such a group is also called one by one.
+    A LinearBatch is built per forward (a few ctypes arrays; nothing is cached by data pointer)."""
+
+    def __init__(self, layers):
+        super().__init__()
+        layers = list(layers)
+        if not layers or not all(isinstance(l, SparseLinear) for l in layers):
+            raise TypeError("layers must be a non-empty list of SparseLinear modules")
+        self.layers = torch.nn.ModuleList(layers)
+
+    def forward(self, x, residuals=None):
+        """x: one tensor (..., in_features) that every layer reads, or a list with one tensor per layer (their
+        leading shapes -- token counts -- may differ).  residuals: None, or a list with None or a tensor
+        per layer.  Returns the list of outputs, (..., out_features) each."""
+        n = len(self.layers)
+        xs = [x] * n if isinstance(x, torch.Tensor) else list(x)
+        res = [None] * n if residuals is None else list(residuals)
+        if len(xs) != n or len(res) != n:
+            raise ValueError(f"x and residuals must hold one item per layer ({n})")
+        flat = [l._flatten(xi, ri) for l, xi, ri in zip(self.layers, xs, res)]
+        if isinstance(x, torch.Tensor):  # one flattened x for every layer, not n copies of a strided one
+            flat = [(lead, flat[0][1], r) for lead, _, r in flat]
+        alone = len({id(l.plan) for l in self.layers}) != n
+        if alone or any(l._wants_grad(x2, r) for l, (_, x2, r) in zip(self.layers, flat)):
+            return [l(xi, ri) for l, xi, ri in zip(self.layers, xs, res)]
+        entries, epis, outs = [], [], []
+        for l, (lead, x2, r) in zip(self.layers, flat):
+            out = torch.empty((x2.shape[0], l.out_features), dtype=x2.dtype, device=x2.device)
+            bias = l.bias.detach() if isinstance(l.bias, torch.nn.Parameter) else l.bias
+            entries.append((l.plan, 0, x2, out))
+            epis.append({"bias": bias, "activation": l.activation, "residual": r})
+            outs.append(out.reshape(lead + (l.out_features,)))
+        LinearBatch(entries, epis).run()
+        return outs

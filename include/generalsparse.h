@@ -223,6 +223,41 @@ int gs_plan_linear_launches(gs_plan_t *p, int n_tokens, int *tiles, int cap);
  * needs no state: only the limit of 16383 tiles per launch splits a call) */
 int gs_linear_tile_split(uint64_t row_blocks, int k_ranges, int row_tiles, int n_tokens, long long ws_kb,
                          unsigned long long *tile_bytes, int *tiles, int cap);
+/* n gs_linear calls as one call on one stream: entry i is gs_linear(plans[i], replicas[i], X[i], Y[i],
+ * n_tokens[i], epi[i], stream) -- its own plan, operands and token count; epi may be NULL, and so may any
+ * epi[i]; several entries may read one X.  Consecutive entries that gs_linear would each run as ONE
+ * k_mfma_ks_tm launch of the same instantiation run as ONE launch of k_mfma_ks_tm_group -- one grid, each entry
+ * on its own share of it, with its own token tiles -- so a model's Q/K/V projections, an MLP's gate / up pair or
+ * a set of experts with ragged token counts pay one launch instead of one each.  An entry's Y has the bits
+ * of its own gs_linear call, grouped or not.  Entries share a launch when all of this holds for each:
+ * gs_plan_linear_fused = 1, X 16-byte aligned, 16-bit weights (not GS_W_FP8_E4M3), a single launch under
+ * LINEAR_WS_KB (gs_plan_linear_launches = 1), and the same dtype, KS_NT, row tiles and entry groups per k-step
+ * as its neighbours; at most gs_linear_group_max() (32) entries per launch, and a (plan, replica) that repeats
+ * starts a new launch (it would share K-split tickets and slabs: give such layers replicas of their own,
+ * gs_plan_add_replica).  Every other entry, and a run of one entry, goes through gs_linear's own code:
+ * FP8 weights, the gather families, a misaligned X, LINEAR_FUSE = 0, a call LINEAR_WS_KB splits.
+ * gs_linear_batch_launches tells the launches.  The epilogue is applied in the grouped kernel's store (one
+ * rounding), as in k_mfma_ks_tm.  K-split state: a grouped entry with K ranges and more than one token tile runs on
+ * its replica's gs_linear state (allocated by the first call that needs it -- refused inside stream capture that
+ * first time -- and zeroed on the stream ahead of the launch where it may hold another tile count's layout), an
+ * entry of one tile on the upload's own; a timeout of the K-split combine reaches gs_plan_device_status as from
+ * gs_linear.  Refused (GS_ERR) before the first launch, every Y untouched: a null plan, X or Y, a plan that
+ * is not on the device, a bad replica, n_tokens[i] < 1, an invalid epilogue, a residual that overlaps its Y. */
+int gs_linear_batch(gs_plan_t *const *plans, const int *replicas, const void *const *X, void *const *Y,
+                    const int *n_tokens, const gs_epilogue *const *epi, int n, gs_stream_t stream);
+/* how gs_linear_batch would enqueue these entries: returns the number of launches and writes the entries of
+ * each to entries_per_launch[0 .. min(count, cap)), in order.  A grouped launch counts its entries; an entry
+ * that runs through gs_linear counts as 1, whatever gs_linear enqueues for it.  < 0: a bad argument, a plan
+ * that is not on the device, a bad replica.  Allocates nothing. */
+int gs_linear_batch_launches(gs_plan_t *const *plans, const int *replicas, const void *const *X, const int *n_tokens,
+                             int n, int *entries_per_launch, int cap);
+/* the grid of one grouped launch, host only: entry i of n has nwg[i] workgroups per token tile (row blocks x
+ * K ranges) and tiles[i] token tiles, and owns workgroups [begin[i], begin[i] + nwg[i] * tiles[i]); every begin
+ * is a multiple of 8 and begin[n] is the grid.  GS_ERR, begin untouched: n < 1 or past gs_linear_group_max(), an
+ * entry without workgroups, a grid past 2^31 - 1. */
+int gs_linear_group_layout(const uint32_t *nwg, const uint32_t *tiles, int n, uint32_t *begin);
+/* the most entries of one grouped launch (the kernel's arguments fit the 4 KB kernarg segment) */
+int gs_linear_group_max(void);
 /* The plan's pattern in one canonical order, host only: by original row, then by column; stored duplicates
  * of one coordinate are adjacent and keep their input order (for a row-major dense weight: the order of
  * its non-zeros).  row / col / val receive the original row, the column and the fp32 value the plan
